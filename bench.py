@@ -10,7 +10,7 @@ triplet + R replayed triplets that is already resident in HBM when the timed reg
 what slam/slam.py:181-188 does with the result every frame: the online sample's pose and every loss scalar read back to
 the host (`--no-readback` leaves that out), on the product's DEFAULT boundary -- outputs and losses are device tensors
 exactly like the reference's (`--host-outputs` times the opt-in host-output path instead).  The PCIe-inclusive frame of SURVEY.md 8(d) (pinned host minibatch -> H2D
-inside adapt()) is measured by the same run and reported under `also.end_to_end`; by the contract it is never `value`.
+inside adapt()) is measured by the same run with `--full` and reported under `also.end_to_end`; by the contract it is never `value`.
 N = 1 runs BASELINE config 3 (R = 4, B = 5, the configuration the 30 frames/s target is quoted on);
 `--replay R` selects another replay count (R = 0 is BASELINE config 2).
 N > 1 shards a minibatch data-parallel with ONE sum-all-reduce of the flat gradient arena per step over
@@ -20,10 +20,20 @@ grows ("weak").  `--total-replay K` instead shards a minibatch of 1+K triplets a
 (`--gpus 8 --total-replay 32` is BASELINE config 4: shards 5,4,4,4,4,4,4,4).  `value` counts frames of
 (1+R) triplets: value = steps/s * B/(1+R), so N = 1 is plain frames/s.
 
-Rank 0 prints ONE JSON line (contract in the task description) with `roofline` (dominant kernel:
-the fp32-MFMA conv, algorithmic FLOPs / the launches' own start-stop HIP events -- hipExtLaunchKernel
-timestamps taken by the library, the duration rocprofv3 reports -- vs the 157.3 TFLOP/s fp32 matrix peak) and `cpu_baseline` (the oracle's torch-CPU restatement of the same step, timed on
-this box's host cores on a bounded sample).
+Rank 0 prints ONE JSON line (contract in the task description).  A plain run sets up, warms up (`--warmup W` steps), times
+EXACTLY `--steps K` steps (one timed block; `--blocks n` repeats it and reports the median block), writes the last timed step's
+outputs if `--dump-outputs DIR` is given, and prints that line.  Everything else is measured only with `--full`:
+`roofline` (dominant kernel: the fp32-MFMA conv, algorithmic FLOPs / the launches' own start-stop HIP events --
+hipExtLaunchKernel timestamps taken by the library, the duration rocprofv3 reports -- vs the 157.3 TFLOP/s fp32 matrix peak),
+`cpu_baseline` (the oracle's torch-CPU restatement of the same step, timed on this box's host cores on a bounded sample),
+`repeated_blocks` (the timed block run 25 more times: spread and bitwise replica check), `also` (the reference's 5-step frame and
+the end-to-end frame) and, with N > 1, `gradient_exchange`.
+
+`--dump-outputs DIR` writes what the caller of the timed path receives from its last step -- every tensor of the outputs dict
+adapt() returns, every loss scalar and, with `--lcd`, the loop-closure feature -- as DIR/<name>.npy (float32; the key's parts
+joined by '_', loss keys prefixed `loss_`).  An array larger than the per-array cap (64 MB in all) is written as a fixed sample
+of its flattened elements: the same seeded indices for the same shape, so two builds compare output for output.  The inputs
+(weights, minibatch, tie-break noise) are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -40,6 +50,7 @@ os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
 import torch  # noqa: E402
 
 FP32_MFMA_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 / 16x16x4_f32
+REPEAT_BLOCKS = 25              # --full: extra timed blocks for the spread of the headline statistic
 
 
 def build_predictor(H, W, B_cfg, host_outputs=False):
@@ -106,13 +117,54 @@ def cpu_baseline(H, W, B, budget_s=25.0):
                       + ', '.join(f'{n}: {t:.2f}' for n, t in sweep.items()) + ')'}
 
 
+DUMP_MAX_BYTES = 64 << 20       # all arrays of --dump-outputs together
+DUMP_MAX_ELEMS = 1 << 19        # per array (2 MB of float32); a larger output is written as a seeded sample of its elements
+
+
+def dump_outputs(out_dir, outputs, losses, lcd_feature=None):
+    """The last timed step's results as out_dir/<name>.npy in float32 (float64 stays float64).  Arrays above the per-array cap
+    are flattened and sampled at indices drawn from a generator seeded with 0: a function of the array's size only."""
+    import re
+    import numpy as np
+
+    def name_of(key):
+        parts = key if isinstance(key, tuple) else (key,)
+        return re.sub(r'[^A-Za-z0-9_.-]', '_', '_'.join(str(x) for x in parts))
+    arrays = {name_of(k): v for k, v in outputs.items() if isinstance(v, torch.Tensor)}
+    arrays.update({'loss_' + name_of(k): v for k, v in losses.items() if isinstance(v, torch.Tensor)})
+    if lcd_feature is not None:
+        arrays['lcd_feature'] = lcd_feature
+    # the small arrays (pose, losses, features) whole; the 64 MB that remain shared by the large ones (8 bytes per element:
+    # float64 at worst)
+    small = [t for t in arrays.values() if t.numel() <= 4096]
+    budget = DUMP_MAX_BYTES - sum(8 * t.numel() for t in small)
+    cap = max(4096, min(DUMP_MAX_ELEMS, budget // (8 * max(1, len(arrays) - len(small)))))
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    total, sampled = 0, []
+    for name, t in sorted(arrays.items()):
+        a = t.detach().to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32)
+        if a.numel() > cap:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        a = a.numpy()
+        np.save(out_dir / f'{name}.npy', a)
+        total += a.nbytes
+    assert total <= DUMP_MAX_BYTES, total
+    return {'dir': str(out_dir), 'arrays': len(arrays), 'bytes': total, 'sampled': sampled, 'sample_elements': cap}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)      # 0.33 s timed at 3.2 ms per step
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--blocks', type=int, default=25, help='how many times the timed block of `steps` steps is repeated; the median '
+    ap.add_argument('--blocks', type=int, default=1, help='how many times the timed block of `steps` steps is repeated; the median '
                     'block is reported (ms_per_step), min / max beside it')
+    ap.add_argument('--full', action='store_true', help='also measure everything beside the headline: roofline pass, CPU baseline, '
+                    'repeated blocks, 5-step and end-to-end frames, per-rank gradient exchange (off: only the timed steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step as DIR/<name>.npy')
     ap.add_argument('--replay', type=int, default=4, help='replay triplets of the N=1 minibatch; every rank gets 1+replay triplets')
     ap.add_argument('--total-replay', type=int, default=None, help='shard a minibatch of 1+K triplets over the ranks instead '
                     '(8 GPUs, K=32: BASELINE config 4)')
@@ -137,6 +189,8 @@ def main():
                     'ranks share one GPU for a functional check of the sharded path)')
     ap.add_argument('--dump-convs', action='store_true', help='per-launch conv timings to stderr')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1')
     H, W, N = args.height, args.width, args.gpus
 
     rank = int(os.environ.get('RANK', '0'))
@@ -232,12 +286,14 @@ def main():
         since_restore[0] += steps
         return p.adapt(None, data, steps=steps)
 
+    last_lcd = [None]
+
     def step():
         out = train(batch, S)
         if not args.no_readback:
             consume(*out)
         if lcd_enc is not None:      # slam.py:223: after the pose has been read back, on the rank that holds the online frame
-            lcd_enc(lcd_image)
+            last_lcd[0] = lcd_enc(lcd_image)
         return out
 
     def sync():
@@ -249,38 +305,54 @@ def main():
         step()
     snapshot_state()
     # The timed region of the contract -- barrier + synchronize, EXACTLY `steps` steps, barrier + synchronize, MAX over ranks -- is
-    # run `blocks` times back to back (default 25: ~1.7 s of GPU work at 3.3 ms per step, so that the driver's utilisation
-    # sampler sees the GPU busy) and the MEDIAN block is reported; min / max are printed beside it.  `steps` x `ms_per_step`
-    # describes one block.  (One 65 ms block, as in rounds 1-4, moved by +-1 % from run to run -- the size of every gain claimed
-    # since round 2.)
-    block_s = []
-    block_end_loss = []
-    for _ in range(max(1, args.blocks)):
-        restore_state()          # every block times the same `steps` optimizer steps
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            outputs, losses = step()
-        sync()
-        dt = time.perf_counter() - t0
-        if N > 1:
-            t = torch.tensor([dt], device=dev, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t.item())
-        block_s.append(dt)
-        block_end_loss.append(float(losses['loss']))
-    # the blocks are replicas of one another down to the last bit (same state, same minibatch, same noise draws, fixed
-    # summation orders) -- reported, not asserted: `blocks_identical` false would mean the restore above is not ordered
-    blocks_identical = len(set(block_end_loss)) == 1
-    ordered = sorted(block_s)
+    # run `blocks` times back to back (default 1) and the MEDIAN block is reported; min / max are printed beside it.  `steps` x
+    # `ms_per_step` describes one block.  (One 65 ms block moved by +-1 % from run to run: time enough steps, or look at the
+    # spread of `repeated_blocks` under --full.)
+    def timed_blocks(n_blocks):
+        block_s, block_end_loss = [], []
+        for _ in range(n_blocks):
+            restore_state()          # every block times the same `steps` optimizer steps
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                outputs, losses = step()
+            sync()
+            dt = time.perf_counter() - t0
+            if N > 1:
+                t = torch.tensor([dt], device=dev, dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                dt = float(t.item())
+            block_s.append(dt)
+            block_end_loss.append(float(losses['loss']))
+        # the blocks are replicas of one another down to the last bit (same state, same minibatch, same noise draws, fixed
+        # summation orders) -- reported, not asserted: `blocks_identical` false would mean the restore above is not ordered
+        ordered = sorted(block_s)
+        return ordered, len(set(block_end_loss)) == 1, outputs, losses
+
+    ordered, blocks_identical, outputs, losses = timed_blocks(max(1, args.blocks))
     dt = ordered[len(ordered) // 2]
     ms = dt / args.steps * 1e3
     ms_min, ms_max = ordered[0] / args.steps * 1e3, ordered[-1] / args.steps * 1e3
     value = (args.steps / dt) * (B / FRAME_TRIPLETS)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before any further step (--full's extra passes) can replace them
+        dumped = dump_outputs(args.dump_outputs, outputs, losses, last_lcd[0])
+    loss_last = float(losses['loss'])
+
+    # ---- --full: the timed block 25 more times (spread of the headline's statistic, replica check of the restore) ---------
+    repeated = None
+    if args.full:
+        r_ordered, r_identical, _, r_losses = timed_blocks(REPEAT_BLOCKS)
+        repeated = {'blocks': REPEAT_BLOCKS, 'steps_per_block': args.steps,
+                    'ms_per_step_median': round(r_ordered[len(r_ordered) // 2] / args.steps * 1e3, 3),
+                    'ms_per_step_min': round(r_ordered[0] / args.steps * 1e3, 3),
+                    'ms_per_step_max': round(r_ordered[-1] / args.steps * 1e3, 3),
+                    'blocks_identical': r_identical and float(r_losses['loss']) == loss_last}
 
     # ---- SURVEY.md 8(d)'s end-to-end frame: pinned host batch -> adapt() (H2D inside) -> pose + losses on the host -------
     e2e = None
-    if rank == 0 and N == 1 and not args.no_also:
+    if args.full and rank == 0 and N == 1 and not args.no_also:
         host = {k: v.pin_memory() for k, v in shard.items()}
 
         def frame():
@@ -343,7 +415,7 @@ def main():
                            '(slam.py:181-188)' + (', loop-closure encoder forward (slam.py:223)' if lcd_enc is not None else '')}
 
     also = None
-    if N == 1 and S == 1 and not args.no_also:
+    if args.full and N == 1 and S == 1 and not args.no_also:
         # the reference's shipped configuration (config_adapt.yaml:53, adaptation_epochs: 5): five optimizer steps
         # per incoming frame; steps 2..5 keep the frozen encoders' features (engine.forward reuse_frozen).
         # Best of three groups of six calls (a reported extra, not the headline: one noisy group should not move it).
@@ -366,7 +438,7 @@ def main():
 
     # ---- multi-GPU diagnosis (outside the timed region): every rank times its three bucket all-reduces on the tail stream ------
     exchange = None
-    if N > 1:
+    if args.full and N > 1:
         eng = p.engine
         reports = []
         for _ in range(5):
@@ -394,9 +466,9 @@ def main():
 
     # ---- roofline of the dominant kernel (instrumented extra step, outside the timed region) ------
     roof = None
-    if rank != 0 and N > 1:
+    if args.full and rank != 0 and N > 1:
         step(); step()          # the two extra (collective) steps of rank 0's instrumented pass below
-    if rank == 0:
+    if args.full and rank == 0:
         # serial launch order for this pass: with the pose / wgrad side streams active several kernels share
         # the GPU and a launch's own duration is not its kernel's efficiency
         p.engine.use_side_stream = False
@@ -481,14 +553,14 @@ def main():
         roof['all_conv_launches']['winograd'] = {'launches': sum(a[2] for (k_, c_), a in agg.items() if c_ == 40),
                                                  'gflop_per_step': round(wfl / 1e9, 2), 'time_ms_per_step': round(wt * 1e3, 3)}
     cpu = None
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and N == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(H, W, B)
     if rank == 0:
         line = {
             'metric': 'online-adapt frames/sec @192x640 (1 triplet + K replay)',
             'value': round(value, 3), 'unit': 'frames/s', 'n_gpus': N, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(ms, 3), 'ms_per_step_min': round(ms_min, 3), 'ms_per_step_max': round(ms_max, 3),
-            'timed_blocks': len(block_s), 'blocks_identical': blocks_identical, 'state_restored_every_steps': RESTORE_EVERY, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'timed_blocks': len(ordered), 'blocks_identical': blocks_identical, 'state_restored_every_steps': RESTORE_EVERY, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f32', 'data': 'synthetic (uniform-random images, lr 1e-12)' if args.random_images else 'synthetic',
             'config': {'workload': f'DepthPosePrediction.adapt(steps={S}), {H}x{W}, 1 online + K={K} replay triplets '
                                    f'(global batch {B}); ResNet-18 depth+pose nets, closed-form random-init weights; '
@@ -504,10 +576,14 @@ def main():
                                    'reference default: outputs and losses are device tensors; the training step runs detached on '
                                    'the engine stream (the read-back waits for the forward + 3 launches)',
                        'lcd_encoder_in_frame': bool(args.lcd),
-                       'loss': float(losses['loss'])},
+                       'loss': loss_last},
             'build_id': build_id,
-            'roofline': roof, 'cpu_baseline': cpu,
+            'roofline': roof, 'cpu_baseline': cpu, 'full': bool(args.full),
         }
+        if repeated is not None:
+            line['repeated_blocks'] = repeated
+        if dumped is not None:
+            line['dumped_outputs'] = dumped
         if exchange is not None:
             line['gradient_exchange'] = exchange
         if also is not None:

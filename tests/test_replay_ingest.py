@@ -158,8 +158,8 @@ class _SlamShapedLikeTheReference:
 
 @pytest.mark.parametrize('backend', BACKENDS)
 def test_install_switches_a_replay_buffer_and_a_slam_object_over(backend, tmp_path):
-    """install() on objects with the reference's calling pattern (the reference itself runs in tests/test_reference_callers.py, build
-    container only; this twin also runs on the MI355X): `get` builds the K samples in ONE get_many() -- bitwise what get_many()
+    """install() on objects with the reference's calling pattern (the reference's own objects
+    need a reference checkout, which the repository does not hold; this test also runs on the MI355X): `get` builds the K samples in ONE get_many() -- bitwise what get_many()
     returns for those files with the same `random` state --, the object's own `_get` is never entered, `_cat_dict` joins a host
     sample with the device minibatch, and the classes are untouched (another instance still runs its own code)."""
     from PIL import Image

@@ -91,7 +91,7 @@ def test_api_corners_match_oracle(backend):
 
 @pytest.mark.parametrize('backend', BACKENDS)
 def test_mini_slam_loop(backend, tmp_path, monkeypatch):
-    """GPU twin of tests/test_reference_callers.py (the reference checkout does not travel to the GPU box): the
+    """The reference's driver loop without the reference checkout (which the repository does not hold): the
     per-frame sequence of slam/slam.py:137-243 on the product packages alone -- encoder descriptor -> replay buffer
     bookkeeping through the `faiss`-named module (the calls of replay_buffer.py:95-160) and through DiversityBuffer,
     adapt() on online + replayed samples, LoopClosureDetection.add/search, predict_pose on a detected loop."""

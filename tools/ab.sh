@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of environment knobs inside ONE gpurun call (same box, same clocks):  bash tools/ab.sh "<bench args>" "VAR=1" "VAR=2 OTHER=x" ...
 # prints ms per step (median of the timed blocks), min / max and the 5-step frame per variant; "-" = no extra environment.
-ARGS=${1:---steps 20 --warmup 5 --blocks 9 --no-cpu-baseline}
+ARGS=${1:---full --steps 20 --warmup 5 --blocks 9 --no-cpu-baseline}
 shift
 for v in "$@"; do
     if [ "$v" == "-" ]; then e=""; else e="$v"; fi

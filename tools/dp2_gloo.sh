@@ -9,7 +9,7 @@ run() {  # label, env, bench args
     local label=$1; local envs=$2; shift 2
     echo "== $label ($envs)"
     env $envs python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29631 \
-        bench.py --gpus 2 --backend gloo --no-cpu-baseline --no-also "$@" 2>/tmp/dp2.err | brief || tail -5 /tmp/dp2.err
+        bench.py --full --gpus 2 --backend gloo --no-cpu-baseline --no-also "$@" 2>/tmp/dp2.err | brief || tail -5 /tmp/dp2.err
 }
 for tail in 1 0; do
     run "192x640, shards 3+2 (BASELINE config 4 shard sizes)" "CLSLAM_ASYNC_TAIL=$tail" --total-replay 4 --steps 20 --warmup 5

@@ -15,25 +15,25 @@ python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/${T
 # counter passes FIRST: bench.py below then finds a counter file of ITS build and reports roofline.traffic from it
 for ctr in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_$ctr
-    (cd /tmp && CLSLAM_SIDE_STREAM=0 rocprofv3 --pmc $ctr -d /tmp/pmc_$ctr -o run -- python $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-also > /tmp/pmc_$ctr.log 2>&1)
+    (cd /tmp && CLSLAM_SIDE_STREAM=0 rocprofv3 --pmc $ctr -d /tmp/pmc_$ctr -o run -- python $OLDPWD/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-also > /tmp/pmc_$ctr.log 2>&1)
     db=$(ls /tmp/pmc_$ctr/*/*.db /tmp/pmc_$ctr/*.db 2>/dev/null | head -1)
     python tools/pmc_summary.py $db conv > $OUT/${TAG}_pmc_$ctr.txt 2>&1
     eval "DB_$ctr=$db"
 done
 # MFMA-busy evidence (north_star: "rocprof ... MFMA-busy against gfx950 peak"): two more counter passes of the same build
 rm -rf /tmp/pmc_sqA /tmp/pmc_sqB
-(cd /tmp && CLSLAM_SIDE_STREAM=0 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -d /tmp/pmc_sqA -o run -- python $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-also > /tmp/pmc_sqA.log 2>&1)
-(cd /tmp && CLSLAM_SIDE_STREAM=0 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES -d /tmp/pmc_sqB -o run -- python $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-also > /tmp/pmc_sqB.log 2>&1)
+(cd /tmp && CLSLAM_SIDE_STREAM=0 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -d /tmp/pmc_sqA -o run -- python $OLDPWD/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-also > /tmp/pmc_sqA.log 2>&1)
+(cd /tmp && CLSLAM_SIDE_STREAM=0 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES -d /tmp/pmc_sqB -o run -- python $OLDPWD/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-also > /tmp/pmc_sqB.log 2>&1)
 python tools/pmc_mfma_busy.py $(ls /tmp/pmc_sqA/*/*.db /tmp/pmc_sqA/*.db 2>/dev/null | head -1) $(ls /tmp/pmc_sqB/*/*.db /tmp/pmc_sqB/*.db 2>/dev/null | head -1) conv > $OUT/${TAG}_pmc_mfma_busy.txt 2>&1
 # L2-miss traffic per launch of every conv kernel, keyed by kernel name: bench.py's roofline.traffic reads THIS file
 python tools/pmc_traffic.py $DB_FETCH_SIZE $DB_WRITE_SIZE $OUT/${TAG}_pmc_traffic.json > $OUT/${TAG}_pmc_traffic.log 2>&1
 cp $OUT/${TAG}_pmc_traffic.json profiles/pmc_traffic.json
-python bench.py --dump-convs > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python bench.py --full --dump-convs > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 grep "^# conv" $OUT/${TAG}_bench.err > $OUT/${TAG}_conv_launches.txt
 prof() {   # name, env..., then bench args after --
     local name=$1; shift
     rm -rf /tmp/prof_$name
-    (cd /tmp && env "$@" rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o run -- python $OLDPWD/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-also > /tmp/prof_$name.log 2>&1)
+    (cd /tmp && env "$@" rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o run -- python $OLDPWD/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-also > /tmp/prof_$name.log 2>&1)
     local db=$(ls /tmp/prof_$name/*/*.db /tmp/prof_$name/*.db 2>/dev/null | head -1)
     python tools/rocprof_summary.py $db $OUT/${TAG}_kernel_stats_$name.csv
     if [ "$name" == "3streams" ]; then python tools/timeline.py $db -5 > $OUT/${TAG}_timeline_one_step.txt 2>&1; fi
@@ -46,11 +46,11 @@ rm -rf /tmp/prof_rccl1
 { tail -1 /tmp/prof_rccl1.log; python tools/timeline.py $(ls /tmp/prof_rccl1/*/*.db /tmp/prof_rccl1/*.db 2>/dev/null | head -1) -2; } > $OUT/${TAG}_rccl1_timeline.txt 2>&1
 brief() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print({k: d.get(k) for k in ('value', 'unit', 'ms_per_step', 'also')}, d['config']['workload'][:70])"; }
 {
-  for r in 0 2 32; do echo "== 192x640 replay $r"; python bench.py --replay $r --steps 20 --warmup 5 --no-cpu-baseline | brief; done
-  echo "== 192x640 replay 4, uniform-random images"; python bench.py --random-images --steps 20 --warmup 5 --no-cpu-baseline --no-also | brief
-  echo "== 384x1280 replay 8"; python bench.py --height 384 --width 1280 --replay 8 --steps 10 --warmup 3 --no-cpu-baseline | brief
-  echo "== 384x1280 replay 8 + loop-closure encoder forward in every frame (BASELINE config 5 on one GPU, ONE number)"; python bench.py --height 384 --width 1280 --replay 8 --lcd --steps 10 --warmup 3 --no-cpu-baseline | brief
-  echo "== 192x640 replay 4, opt-in host-output path"; python bench.py --host-outputs --steps 50 --warmup 5 --no-cpu-baseline --no-also | brief
+  for r in 0 2 32; do echo "== 192x640 replay $r"; python bench.py --full --replay $r --steps 20 --warmup 5 --no-cpu-baseline | brief; done
+  echo "== 192x640 replay 4, uniform-random images"; python bench.py --full --random-images --steps 20 --warmup 5 --no-cpu-baseline --no-also | brief
+  echo "== 384x1280 replay 8"; python bench.py --full --height 384 --width 1280 --replay 8 --steps 10 --warmup 3 --no-cpu-baseline | brief
+  echo "== 384x1280 replay 8 + loop-closure encoder forward in every frame (BASELINE config 5 on one GPU, ONE number)"; python bench.py --full --height 384 --width 1280 --replay 8 --lcd --steps 10 --warmup 3 --no-cpu-baseline | brief
+  echo "== 192x640 replay 4, opt-in host-output path"; python bench.py --full --host-outputs --steps 50 --warmup 5 --no-cpu-baseline --no-also | brief
 } > $OUT/${TAG}_other_configs.txt 2>&1
 BENCH_WGRAD=1 python tools/bench_conv.py 5 30,31,32,33 > $OUT/${TAG}_conv_microbench.txt 2>&1
 BENCH_WGRAD=0 python tools/bench_conv.py 1 30,31,32,33 > $OUT/${TAG}_conv_microbench_b1.txt 2>&1
@@ -73,7 +73,7 @@ bash tools/pmc_calib.sh > $OUT/${TAG}_pmc_calibration.txt 2>&1
 { for m in mfma_clock mfma_valu_share lds_dma_rate event_gap ext_launch_cost; do echo "== tools/micro/$m.hip"; hipcc --offload-arch=gfx950 -O3 -o /tmp/$m tools/micro/$m.hip 2>/dev/null && /tmp/$m; done; } > $OUT/${TAG}_micro_calibration.txt 2>&1
 # one decoder-only step (steps 2..5 of adapt(steps=5)) as a kernel timeline
 rm -rf /tmp/prof_s5
-(cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_s5 -o run -- python $OLDPWD/bench.py --adapt-steps 5 --steps 6 --warmup 2 --blocks 1 --no-also --no-cpu-baseline > /tmp/prof_s5.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_s5 -o run -- python $OLDPWD/bench.py --full --adapt-steps 5 --steps 6 --warmup 2 --blocks 1 --no-also --no-cpu-baseline > /tmp/prof_s5.log 2>&1)
 python tools/timeline.py $(ls /tmp/prof_s5/*/*.db /tmp/prof_s5/*.db 2>/dev/null | head -1) -14 > $OUT/${TAG}_timeline_reuse_step.txt 2>&1
 python tools/bench_small.py > $OUT/${TAG}_small_kernels.txt 2>&1
 python tools/bench_reduce.py > $OUT/${TAG}_reduce.txt 2>&1
