@@ -658,3 +658,40 @@ def loss_bwd2_pyramid(disps, sel, coef_sel, warped, target, src_m1, src_p1, inv_
     _lib.get_lib().call('clslam_loss_bwd2_pyramid_range', _ptr4(disps), _pa(sel, torch.uint8), _p(coef_sel), _p(warped), _p(target),
                         _p(src_m1), _p(src_p1), _p(inv_k), _p(proj), _p(sample_w), _p(ddisp_up), _pa(dp_partial, torch.float64), B, H, W,
                         _nd(min_depth), _nd(max_depth), scales[0], scales[1], _stream(ddisp_up))
+
+
+# ---- SE(3) pose-graph optimisation (csrc/pose_graph.hip; the Levenberg control is clslam_hip/pose_graph.py) ----------------
+def _pd(t):
+    return _pa(t, torch.float64)
+
+
+def _pi(t):
+    return _pa(t, torch.int32)
+
+
+def pgo_lin_stride() -> int:
+    return _query('clslam_pgo_lin_stride')
+
+
+def pgo_solve_workspace(na: int) -> int:
+    return _query('clslam_pgo_solve_workspace', na)
+
+
+def pgo_edge_eval(est, edge_v, meas, err, jac_i, jac_j, stream):
+    _lib.get_lib().call('clslam_pgo_edge_eval', _pd(est), _pi(edge_v), _pd(meas), edge_v.shape[0], _pd(err), _pd(jac_i), _pd(jac_j),
+                        stream)
+
+
+def pgo_build_system(est, edge_v, meas, info, huber, ne, cptr, contrib, diag, nnzb, na, lin, H, b, scal, stream):
+    _lib.get_lib().call('clslam_pgo_build_system', _pd(est), _pi(edge_v), _pd(meas), _pd(info), _pd(huber), ne, _pi(cptr),
+                        _pi(contrib), _pi(diag), nnzb, na, _pd(lin), _pd(H), _pd(b), _pd(scal), stream)
+
+
+def pgo_solve(H, rptr, col, tri, b, lam, na, tol, max_iter, delta, work, scal, stream):
+    _lib.get_lib().call('clslam_pgo_solve', _pd(H), _pi(rptr), _pi(col), _pi(tri), _pd(b), float(lam), na, float(tol), int(max_iter),
+                        _pd(delta), _pd(work), _pd(scal), stream)
+
+
+def pgo_update_score(est, trial, act, nv, delta, edge_v, meas, info, huber, ne, robust, scal, out_index, stream):
+    _lib.get_lib().call('clslam_pgo_update_score', _pd(est), _pd(trial), _pi(act), nv, _pd(delta), _pi(edge_v), _pd(meas), _pd(info),
+                        _pd(huber), ne, int(robust), _pd(scal), int(out_index), stream)

@@ -468,6 +468,36 @@ int clslam_se_gate(const float* pool, const float* w1, const float* b1, const fl
 /* x[b][p][c] *= gate[b][c] (in place)                                                             */
 int clslam_channel_scale(float* x, const float* gate, int batch, int hw, int ch, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SE(3) pose-graph optimisation, fp64 (csrc/pose_graph.hip; conventions in its header): the g2o back end of the reference
+ * (slam/pose_graph_optimization.py:1-35,55-77 g2o.SparseOptimizer + BlockSolverSE3 + OptimizationAlgorithmLevenberg over
+ * VertexSE3 / EdgeSE3; slam/slam.py:110-115,203-216,241-246 add_vertex / add_edge / optimize(max_iterations=10000)).  The
+ * Levenberg control runs on the host (clslam_hip/pose_graph.py).  All pointers are device memory; poses are row-major 4x4
+ * doubles indexed by vertex SLOT, edge_v = int32 (from, to) slot pairs, info = the symmetrised 6x6 information matrices,
+ * huber_delta[e] <= 0 = no robust kernel.  No floating-point atomics: every result is bitwise reproducible.
+ * clslam_pgo_edge_eval: err[ne][6] = toVectorMQT(Z^-1 Xi^-1 Xj), jac_i / jac_j[ne][6][6] = d err / d increment of from / to.
+ * clslam_pgo_build_system: linearise every edge into lin[ne][clslam_pgo_lin_stride()], then the block-CSR H (nnzb 6x6 blocks;
+ *   block q = sum of the per-edge blocks contrib[cptr[q] .. cptr[q+1]), code = edge*4 + {0 Hii, 1 Hjj, 2 Hij, 3 Hij^T}) and
+ *   b[na][6] (from the contributions of the diagonal blocks diag[na]); scal[0] = max diag(H).
+ * clslam_pgo_solve: (H + lambda I) delta = -b by PCG in one workgroup, block-tridiagonal preconditioner over consecutive active
+ *   rows (tri[na][3] = block index of (k,k-1), (k,k), (k,k+1), -1 = none), factored by block cyclic reduction; stop at relative
+ *   residual <= tol or max_iter; work = clslam_pgo_solve_workspace(na) doubles.  scal[1] CG iterations, [2] relative residual,
+ *   [3] delta^T (lambda delta - b), [5] 1 if the preconditioner was singular.
+ * clslam_pgo_update_score: trial = est * exp(delta[act[v]]) for act[v] >= 0, est elsewhere (delta NULL: score est itself);
+ *   scal[out_index] = sum over edges of Huber rho(e^T info e) (robust = 0: plain e^T info e).                            */
+int clslam_pgo_edge_eval(const double* est, const int* edge_v, const double* meas, int ne, double* err, double* jac_i,
+                         double* jac_j, void* stream);
+int clslam_pgo_lin_stride(void);
+int clslam_pgo_build_system(const double* est, const int* edge_v, const double* meas, const double* info, const double* huber_delta,
+                            int ne, const int* cptr, const int* contrib, const int* diag, int nnzb, int na, double* lin, double* H,
+                            double* b, double* scal, void* stream);
+int clslam_pgo_solve_workspace(int na);
+int clslam_pgo_solve(const double* H, const int* rptr, const int* col, const int* tri, const double* b, double lambda, int na,
+                     double tol, int max_iter, double* delta, double* work, double* scal, void* stream);
+int clslam_pgo_update_score(const double* est, double* trial, const int* act, int nv, const double* delta, const int* edge_v,
+                            const double* meas, const double* info, const double* huber_delta, int ne, int robust, double* scal,
+                            int out_index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
