@@ -249,7 +249,8 @@ class PoseGraph:
 
     def optimize(self, max_iterations: int) -> int:
         """g2o's Levenberg (module docstring) for at most max_iterations iterations -> iterations done"""
-        stats = {'iterations': 0, 'cg_iterations': [], 'chi2': None, 'lambda': None, 'trials': 0}
+        stats = {'iterations': 0, 'cg_iterations': [], 'cg_residual': [], 'precond_failed': 0, 'chi2': None, 'lambda': None,
+                 'trials': 0}
         self.last_stats = stats
         if max_iterations <= 0 or self.ne == 0:
             return 0
@@ -277,6 +278,8 @@ class PoseGraph:
                     r = self._read()
                     chi2_new = float(r[6])
                     stats['cg_iterations'].append(int(r[1]))
+                    stats['cg_residual'].append(float(r[2]))     # the solver's own ||r|| / ||b|| where it stopped
+                    stats['precond_failed'] += int(r[5] != 0.0)   # preconditioner not factorable: that solve returned d = 0
                     rho = (chi2 - chi2_new) / (float(r[3]) + 1e-3)
                     if rho > 0 and np.isfinite(chi2_new):
                         lam *= max(1.0 / 3.0, min(2.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))

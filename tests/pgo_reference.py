@@ -5,6 +5,9 @@ Huber) and of g2o's Levenberg rule, plus a seeded KITTI-like graph generator.
     exp_mqt / log_mqt / oplus / edge_error / jacobians   batched over a leading axis
     lm(graph, max_iterations)                            dense (or scipy-sparse) Levenberg -> (poses, stats)
     make_graph(n, n_loops, seed, start_id)               ground truth, odometry start, odometry + loop edges
+    jacobians_hp / edge_error_hp / robust_chi2_hp        the same in numpy.longdouble, for the kernel-level tests
+    make_block_system / pcg_reference / ...              block-CSR SPD systems that do not come from a graph, and a plain
+                                                         numpy PCG with an exact block-tridiagonal preconditioner
 
 Nothing here runs on the device; the kernels are checked against it."""
 import numpy as np
@@ -14,16 +17,16 @@ ODOM_COV = np.diag([1.0, 1.0, 0.1, 1.0, 1.0, 0.1])          # slam.py's odometry
 
 
 # ---- chart --------------------------------------------------------------------------------------------------------------
-def exp_mqt(v):
+def exp_mqt(v, dtype=np.float64):
     """(n,6) (t, qxyz) -> (n,4,4); |qxyz|^2 > 1 gives the identity rotation"""
-    v = np.atleast_2d(np.asarray(v, dtype=np.float64))
+    v = np.atleast_2d(np.asarray(v, dtype=dtype))
     x, y, z = v[:, 3], v[:, 4], v[:, 5]
     w2 = 1.0 - (x * x + y * y + z * z)
     bad = w2 < 0
     w = np.sqrt(np.where(bad, 0.0, w2))
     x, y, z = (np.where(bad, 0.0, a) for a in (x, y, z))
     w = np.where(bad, 1.0, w)
-    T = np.zeros((len(v), 4, 4))
+    T = np.zeros((len(v), 4, 4), dtype=dtype)
     T[:, 0, 0] = 1 - 2 * (y * y + z * z); T[:, 0, 1] = 2 * (x * y - z * w); T[:, 0, 2] = 2 * (x * z + y * w)
     T[:, 1, 0] = 2 * (x * y + z * w); T[:, 1, 1] = 1 - 2 * (x * x + z * z); T[:, 1, 2] = 2 * (y * z - x * w)
     T[:, 2, 0] = 2 * (x * z - y * w); T[:, 2, 1] = 2 * (y * z + x * w); T[:, 2, 2] = 1 - 2 * (x * x + y * y)
@@ -35,7 +38,7 @@ def exp_mqt(v):
 def _quat(R):
     """Eigen's matrix -> quaternion (x, y, z, w), one matrix"""
     t = R[0, 0] + R[1, 1] + R[2, 2]
-    q = np.zeros(4)
+    q = np.zeros(4, dtype=R.dtype)
     if t > 0:
         t = np.sqrt(t + 1.0)
         q[3] = 0.5 * t
@@ -59,10 +62,10 @@ def _quat(R):
     return q
 
 
-def log_mqt(T):
+def log_mqt(T, dtype=np.float64):
     """(n,4,4) -> (n,6) (t, xyz of the unit quaternion with w >= 0)"""
-    T = np.asarray(T, dtype=np.float64).reshape(-1, 4, 4)
-    out = np.zeros((len(T), 6))
+    T = np.asarray(T, dtype=dtype).reshape(-1, 4, 4)
+    out = np.zeros((len(T), 6), dtype=dtype)
     for n, M in enumerate(T):
         q = _quat(M[:3, :3])
         q /= np.linalg.norm(q)
@@ -73,8 +76,8 @@ def log_mqt(T):
     return out
 
 
-def inv(T):
-    T = np.asarray(T, dtype=np.float64)
+def inv(T, dtype=np.float64):
+    T = np.asarray(T, dtype=dtype)
     out = np.zeros_like(T)
     Rt = np.swapaxes(T[..., :3, :3], -1, -2)
     out[..., :3, :3] = Rt
@@ -92,22 +95,65 @@ def oplus(X, v):
     return Y
 
 
-def edge_error(Xi, Xj, Z):
-    return log_mqt(inv(Z) @ inv(Xi) @ Xj)
+def edge_error(Xi, Xj, Z, dtype=np.float64):
+    return log_mqt(inv(Z, dtype) @ inv(Xi, dtype) @ np.asarray(Xj, dtype=dtype), dtype)
 
 
-def jacobians(Xi, Xj, Z, h=JAC_STEP):
+def jacobians(Xi, Xj, Z, h=JAC_STEP, dtype=np.float64):
     """(A, B) (n,6,6): central differences of edge_error in the increments of Xi and Xj"""
-    Xi, Xj, Z = (np.asarray(a, dtype=np.float64).reshape(-1, 4, 4) for a in (Xi, Xj, Z))
+    Xi, Xj, Z = (np.asarray(a, dtype=dtype).reshape(-1, 4, 4) for a in (Xi, Xj, Z))
     n = len(Xi)
-    A, B = np.zeros((n, 6, 6)), np.zeros((n, 6, 6))
+    A, B = np.zeros((n, 6, 6), dtype=dtype), np.zeros((n, 6, 6), dtype=dtype)
+    h = dtype(h)
     for k in range(6):
-        v = np.zeros((n, 6))
+        v = np.zeros((n, 6), dtype=dtype)
         v[:, k] = h
-        Ep, Em = exp_mqt(v), exp_mqt(-v)
-        A[:, :, k] = (edge_error(Xi @ Ep, Xj, Z) - edge_error(Xi @ Em, Xj, Z)) / (2 * h)
-        B[:, :, k] = (edge_error(Xi, Xj @ Ep, Z) - edge_error(Xi, Xj @ Em, Z)) / (2 * h)
+        Ep, Em = exp_mqt(v, dtype), exp_mqt(-v, dtype)
+        A[:, :, k] = (edge_error(Xi @ Ep, Xj, Z, dtype) - edge_error(Xi @ Em, Xj, Z, dtype)) / (2 * h)
+        B[:, :, k] = (edge_error(Xi, Xj @ Ep, Z, dtype) - edge_error(Xi, Xj @ Em, Z, dtype)) / (2 * h)
     return A, B
+
+
+# ---- the same in numpy.longdouble (x87 extended where the platform has it: eps 1.1e-19) ----------------------------------
+HP = np.longdouble
+HP_JAC_STEP = 2.0 ** -21        # ~eps_hp^(1/3): truncation (h^2 / 6 |e'''|) and rounding (eps_hp / h) both ~2e-13
+
+
+def edge_error_hp(Xi, Xj, Z):
+    return edge_error(Xi, Xj, Z, HP)
+
+
+def jacobians_hp(Xi, Xj, Z, h=HP_JAC_STEP):
+    """jacobians() carried out in numpy.longdouble end to end (the float64 inputs convert exactly), step for that precision"""
+    return jacobians(Xi, Xj, Z, h, HP)
+
+
+def quat_branch(Rm):
+    """which branch of the matrix -> quaternion conversion a rotation takes: 0 for trace > 0, else 1 + the index of the
+    largest diagonal entry"""
+    Rm = np.asarray(Rm)
+    if Rm[0, 0] + Rm[1, 1] + Rm[2, 2] > 0:
+        return 0
+    i = 0
+    if Rm[1, 1] > Rm[0, 0]:
+        i = 1
+    if Rm[2, 2] > Rm[i, i]:
+        i = 2
+    return 1 + i
+
+
+def quat_to_pose(q_wxyz, t=(0.0, 0.0, 0.0)):
+    """[R(q) t] of a quaternion (w, x, y, z) (normalised here in longdouble), rounded to float64 once at the end"""
+    q = np.asarray(q_wxyz, dtype=HP)
+    q = q / np.sqrt((q * q).sum())
+    w, x, y, z = q
+    T = np.zeros((4, 4), dtype=HP)
+    T[0, :3] = [1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)]
+    T[1, :3] = [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)]
+    T[2, :3] = [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]
+    T[:3, 3] = np.asarray(t, dtype=HP)
+    T[3, 3] = 1
+    return T.astype(np.float64), q.astype(np.float64)
 
 
 def huber(s, delta):
@@ -144,6 +190,17 @@ def robust_chi2(g, poses):
     return float(huber(chi2_terms(g, poses)[1], g.delta)[0].sum())
 
 
+def robust_chi2_hp(g, poses, robust=True):
+    """sum(rho) (robust=False: the plain sum of e^T Omega e) with errors, quadratic forms and the sum in numpy.longdouble"""
+    e = edge_error_hp(poses[g.edges[:, 0]], poses[g.edges[:, 1]], g.meas)
+    s = np.einsum('ni,nij,nj->n', e, g.info.astype(HP), e)
+    if not robust:
+        return s.sum()
+    d = g.delta.astype(HP)
+    use = (d > 0) & (s > d * d)
+    return np.where(use, 2 * d * np.sqrt(np.where(use, s, 1)) - d * d, s).sum()
+
+
 def active_order(g):
     used = np.zeros(len(g.ids), dtype=bool)
     used[g.edges.reshape(-1)] = True
@@ -151,14 +208,15 @@ def active_order(g):
     return act[np.argsort(g.ids[act], kind='stable')]
 
 
-def linear_system(g, poses, sparse=False):
+def linear_system(g, poses, sparse=False, jac=None):
+    """(active order, H, b); jac = (A, B) replaces this module's own Jacobians (to separate assembly from differentiation)"""
     act = active_order(g)
     na = len(act)
     pos = np.full(len(g.ids), -1)
     pos[act] = np.arange(na)
     Xi, Xj = poses[g.edges[:, 0]], poses[g.edges[:, 1]]
     e = edge_error(Xi, Xj, g.meas)
-    A, B = jacobians(Xi, Xj, g.meas)
+    A, B = jacobians(Xi, Xj, g.meas) if jac is None else jac
     s = np.einsum('ni,nij,nj->n', e, g.info, e)
     _, w = huber(s, g.delta)
     W = g.info * w[:, None, None]
@@ -295,3 +353,125 @@ def ate(poses, gt):
 
 def rot_angle(R):
     return float(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1)))
+
+
+# ---- block-CSR SPD systems without a graph, and the PCG reference ------------------------------------------------------
+def band_pairs(na):
+    return [(k, k + 1) for k in range(na - 1)]
+
+
+def make_block_system(na, pairs, seed=0, anchor=0.0, zero_pairs=()):
+    """H = sum over pairs (r, c) of J^T J with one 6x12 J per pair (every term PSD, as an edge's J^T W J is) in the solver's
+    block-CSR layout.  J = D [-(Q1 + N1) | Q2 + N2]: Q orthogonal, D a positive diagonal in [0.5, 2], N Gaussian of size
+    0.3 / sqrt(na) -- dense and different per pair, yet the chain's transfer matrices stay near orthogonal, so the
+    condition number grows like na^2 and not exponentially.  anchor > 0 adds anchor * J0^T J0 (J0 6x6) to block (0, 0): the
+    fixed neighbour that makes H definite without damping.  zero_pairs: pairs drawn with J = 0 (zero information).
+    -> dict(H [nnzb][36], rptr, col, tri, diag, b [na][6], na)"""
+    rng = np.random.default_rng(seed)
+    blocks = {(r, r): np.zeros((6, 6)) for r in range(na)}
+    jit = 0.3 / np.sqrt(na)
+    for r, c in list(pairs) + list(zero_pairs):
+        assert 0 <= r < na and 0 <= c < na and r != c
+        Q1, Q2 = (np.linalg.qr(rng.normal(size=(6, 6)))[0] for _ in range(2))
+        D = np.diag(rng.uniform(0.5, 2.0, 6))
+        J = D @ np.hstack([-(Q1 + jit * rng.normal(size=(6, 6))), Q2 + jit * rng.normal(size=(6, 6))])
+        if (r, c) in zero_pairs:
+            J = 0.0 * J
+        G = J.T @ J
+        blocks[(r, r)] = blocks[(r, r)] + G[:6, :6]
+        blocks[(c, c)] = blocks[(c, c)] + G[6:, 6:]
+        blocks[(r, c)] = blocks.get((r, c), 0) + G[:6, 6:]
+        blocks[(c, r)] = blocks.get((c, r), 0) + G[6:, :6]
+    if anchor > 0:
+        J0 = np.linalg.qr(rng.normal(size=(6, 6)))[0] @ np.diag(rng.uniform(0.5, 2.0, 6))
+        blocks[(0, 0)] = blocks[(0, 0)] + anchor * J0.T @ J0
+    keys = sorted(blocks)
+    index = {k: q for q, k in enumerate(keys)}
+    H = np.stack([blocks[k] for k in keys]).reshape(-1, 36)
+    rows = np.array([k[0] for k in keys])
+    col = np.array([k[1] for k in keys], dtype=np.int32)
+    rptr = np.searchsorted(rows, np.arange(na + 1)).astype(np.int32)
+    tri = np.array([[index.get((r, r - 1), -1), index[(r, r)], index.get((r, r + 1), -1)] for r in range(na)], dtype=np.int32)
+    return {'H': H, 'rptr': rptr, 'col': col, 'tri': tri, 'diag': tri[:, 1].copy(), 'b': rng.normal(size=(na, 6)), 'na': na}
+
+
+def bsr_matrix(H, rptr, col, na, keep=None):
+    """scipy-sparse (csc) matrix of a block-CSR H; keep: the block indices to keep (the others are dropped)"""
+    import scipy.sparse as sp
+    H = np.asarray(H, dtype=np.float64).reshape(-1, 6, 6)
+    rows = np.repeat(np.arange(na), np.diff(rptr))
+    q = np.arange(len(col)) if keep is None else np.asarray(keep)
+    rr, cc = np.meshgrid(np.arange(6), np.arange(6), indexing='ij')
+    i = (6 * rows[q, None, None] + rr).ravel()
+    j = (6 * np.asarray(col)[q, None, None] + cc).ravel()
+    return sp.csc_matrix((H[q].ravel(), (i, j)), shape=(6 * na, 6 * na))
+
+
+def tri_part(H, rptr, col, tri, na):
+    """the block-tridiagonal part the solver's preconditioner keeps (tri's -1 entries are absent blocks)"""
+    t = np.asarray(tri).reshape(-1)
+    return bsr_matrix(H, rptr, col, na, keep=t[t >= 0])
+
+
+def residual_hp(H, rptr, col, na, lam, d, b):
+    """||(H + lam I) d + b|| / ||b|| in numpy.longdouble"""
+    Hh = np.asarray(H).reshape(-1, 6, 6).astype(HP)
+    dh, bh = np.asarray(d).reshape(na, 6).astype(HP), np.asarray(b).reshape(na, 6).astype(HP)
+    rows = np.repeat(np.arange(na), np.diff(rptr))
+    y = HP(lam) * dh + bh
+    np.add.at(y, rows, np.einsum('qij,qj->qi', Hh, dh[np.asarray(col)]))
+    return float(np.sqrt((y * y).sum() / (bh * bh).sum()))
+
+
+def cond_spd(M):
+    """2-norm condition number of a sparse SPD matrix from its extreme eigenvalues (Lanczos; shift-invert at 0 for the
+    smallest); dense below 600 rows"""
+    import scipy.sparse.linalg as spl
+    n = M.shape[0]
+    if n < 600:
+        w = np.linalg.eigvalsh(M.toarray())
+        return float(w[-1] / w[0])
+    hi = spl.eigsh(M, k=1, which='LA', return_eigenvectors=False, tol=1e-6)[0]
+    lo = spl.eigsh(M, k=1, sigma=0.0, which='LM', return_eigenvectors=False, tol=1e-6)[0]
+    return float(hi / lo)
+
+
+def pcg_reference(M, P, b, tol, max_iter, perm=None, iterates=False):
+    """The solver's PCG restated in numpy: M d = -b from d = 0, preconditioner an exact sparse-LU solve with P, the same
+    stopping rule (||r|| <= tol ||b||, tested after the update, or max_iter).  perm: evaluate every dot product and matrix-
+    vector product with the unknowns in this order (a different summation order, the same arithmetic otherwise).
+    -> dict(d, iterations, residual (the recurrence's ||r|| / ||b||), iterates [d after each iteration] if asked)"""
+    import scipy.sparse.linalg as spl
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    n = len(b)
+    M = M.tocsr()
+    if perm is None:
+        dot, mv = np.dot, lambda x: M @ x
+    else:
+        Mp = M[:, perm].tocsr()
+        dot, mv = (lambda x, y: np.dot(x[perm], y[perm])), (lambda x: Mp @ x[perm])
+    d, r = np.zeros(n), -b.copy()
+    rhs2 = dot(r, r)
+    rr, it, its = rhs2, 0, []
+    if rhs2 > 0:
+        lu = spl.splu(P.tocsc())
+        z = lu.solve(r)
+        p = z.copy()
+        rz = dot(r, z)
+        stop2 = tol * tol * rhs2
+        while it < max_iter:
+            q = mv(p)
+            alpha = rz / dot(p, q)
+            d = d + alpha * p
+            r = r - alpha * q
+            rr = dot(r, r)
+            it += 1
+            if iterates:
+                its.append(d.copy())
+            if not rr > stop2:
+                break
+            z = lu.solve(r)
+            rz_new = dot(r, z)
+            p = z + (rz_new / rz) * p
+            rz = rz_new
+    return {'d': d, 'iterations': it, 'residual': float(np.sqrt(rr / rhs2)) if rhs2 > 0 else 0.0, 'iterates': its}

@@ -37,6 +37,17 @@ def _check(P, ref, stats, ref_stats, fixed, tol_t=1e-6, tol_r=1e-7):
     assert np.array_equal(P[fixed], ref[fixed])
 
 
+def _assert_solves_converged(pg):
+    """every linear solve of the last optimize() ended below the iteration cap at the requested residual, and the
+    preconditioner was factorable every time"""
+    from clslam_hip.pose_graph import CG_MAX_ITER, CG_TOL
+    st = pg.last_stats
+    assert len(st['cg_residual']) == len(st['cg_iterations']) == st['trials'] > 0
+    assert max(st['cg_iterations']) < CG_MAX_ITER, st['cg_iterations']
+    assert max(st['cg_residual']) <= CG_TOL, st['cg_residual']
+    assert st['precond_failed'] == 0
+
+
 def _random_pose(rng, big=False):
     T = np.eye(4)
     T[:3, :3] = R._rot(*rng.uniform(-np.pi, np.pi, 3)) if big else R._rot(*rng.normal(0, 0.3, 3))
@@ -118,6 +129,7 @@ def test_lm_matches_dense_reference(backend, n, loops):
         d['poses'][1] = d['poses'][1] @ R.exp_mqt([[0.3, -0.2, 0.1, 0.05, 0.02, -0.03]])[0]
     pg = _pg(d)
     it = pg.optimize(10000)
+    _assert_solves_converged(pg)
     ref, st = R.lm(R.graph_of(d))
     assert it == st['iterations']
     # 600 vertices: chi2 equal to 2.5e-13 relative after the same 44 iterations, but the far end of the chain differs by
@@ -125,6 +137,50 @@ def test_lm_matches_dense_reference(backend, n, loops):
     _check(_poses(pg, d['ids']), ref, pg.last_stats, st, d['fixed'], *((2e-4, 1e-5) if n > 150 else (1e-6, 1e-7)))
     if loops:
         assert R.ate(ref, d['gt']) < R.ate(d['poses'], d['gt'])
+
+
+_CHAIN_CASES = [pytest.param(b.values[0], n, id=f'{n}-{b.id}', marks=b.marks)
+                for b in BACKENDS for n in (3, 10, 33, 150, 300, 700)] + [pytest.param('hip', 1500, id='1500-hip', marks=pytest.mark.gpu)]
+
+
+@pytest.mark.parametrize('backend,n', _CHAIN_CASES)
+def test_loop_free_chain_solves_are_direct(backend, n, monkeypatch):
+    """On a loop-free chain the block-tridiagonal preconditioner is the whole matrix: every solve of optimize() takes no more
+    iterations than a numpy PCG with an exact (sparse-LU) preconditioner takes on the very same H, b and lambda (read back
+    from the device at each solve), plus one.  The reference takes 1 or 2; nothing is hard-coded here."""
+    pytest.importorskip('scipy')
+    import scipy.sparse as sp
+    use_backend(backend)
+    from clslam_hip import ops, pose_graph
+    d = R.make_graph(n, 0, seed=n)
+    rng = np.random.default_rng(n)
+    for k in range(1, n):                       # perturb the start: the odometry chain alone is exactly consistent
+        d['poses'][k] = d['poses'][k] @ R._small_noise(rng, 0.2, 0.02)
+    pg = _pg(d)
+    seen = []
+    real = ops.pgo_solve
+
+    def recording(H, rptr, col, tri, b, lam, na, *rest):
+        nnzb = int(rptr[na].item())
+        seen.append((H[:nnzb].cpu().numpy().copy(), rptr[:na + 1].cpu().numpy(), col[:nnzb].cpu().numpy(), tri[:na].cpu().numpy(),
+                     b[:na].cpu().numpy().copy(), float(lam), na))
+        real(H, rptr, col, tri, b, lam, na, *rest)
+
+    monkeypatch.setattr(ops, 'pgo_solve', recording)
+    it = pg.optimize(20)
+    monkeypatch.undo()
+    _assert_solves_converged(pg)
+    stats = pg.last_stats
+    assert it >= 1 and len(seen) == len(stats['cg_iterations']) and seen[0][-1] == n - 1
+    ref_counts = []
+    for H, rptr, col, tri, b, lam, na in seen:
+        I = sp.identity(6 * na, format='csc')
+        M = R.bsr_matrix(H, rptr, col, na) + lam * I
+        P = R.tri_part(H, rptr, col, tri, na) + lam * I
+        assert abs(M - P).max() == 0.0
+        ref_counts.append(R.pcg_reference(M, P, b, pose_graph.CG_TOL, pose_graph.CG_MAX_ITER)['iterations'])
+    print(f'\nchain {n}: CG iterations {stats["cg_iterations"]}, numpy PCG reference {ref_counts}')
+    assert all(k <= r + 1 for k, r in zip(stats['cg_iterations'], ref_counts))
 
 
 @pytest.mark.parametrize('backend', BACKENDS)
@@ -148,6 +204,7 @@ def test_incremental_growth_like_slam(backend):
         if stage_end == 45:
             pg.add_vertex(-7, iso)                     # isolated
         pg.optimize(10000)
+        _assert_solves_converged(pg)
         sel = [k for k, (a, b) in enumerate(d['edges']) if a < stage_end and b < stage_end]
         g = R.Graph(d['ids'][:stage_end], g_ref_poses[:stage_end], d['fixed'][:stage_end], d['edges'][sel], d['meas'][sel],
                     d['info'][sel])
@@ -168,6 +225,7 @@ def test_no_fixed_vertex_relative_transforms(backend):
     d['fixed'][:] = False
     pg = _pg(d)
     pg.optimize(10000)
+    _assert_solves_converged(pg)
     ref, st = R.lm(R.graph_of(d))
     P = _poses(pg, d['ids'])
     rel = np.einsum('ij,njk->nik', R.inv(P[0]), P)
@@ -184,6 +242,7 @@ def test_huber(backend):
     delta = np.where(np.arange(len(d['edges'])) >= d['n_odom'], 1.0, -1.0)
     pg = _pg(d, delta)
     pg.optimize(10000)
+    _assert_solves_converged(pg)
     ref, st = R.lm(R.graph_of(d, delta))
     _check(_poses(pg, d['ids']), ref, pg.last_stats, st, d['fixed'])
     assert abs(pg.chi2(robust=True) - R.robust_chi2(R.graph_of(d, delta), ref)) <= 1e-9 * st['chi2']
@@ -196,8 +255,10 @@ def test_bitwise_deterministic(backend):
     a, b = _pg(d), _pg(d)
     a.optimize(10000)
     b.optimize(10000)
+    _assert_solves_converged(a)
     assert np.array_equal(_poses(a, d['ids']), _poses(b, d['ids']))
     assert a.last_stats['cg_iterations'] == b.last_stats['cg_iterations']
+    assert a.last_stats['cg_residual'] == b.last_stats['cg_residual']
 
 
 @pytest.mark.parametrize('backend', BACKENDS)

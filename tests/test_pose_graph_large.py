@@ -34,6 +34,7 @@ def test_kitti_sized_graph():
     P = np.stack([pg.get_estimate(int(i)) for i in d['ids']])
     stats = dict(pg.last_stats)
     print(f'\n4541-vertex graph: {it} LM iterations, {wall * 1e3:.1f} ms, CG iterations {stats["cg_iterations"]}, '
+          f'CG relative residuals {["%.2g" % r for r in stats["cg_residual"]]}, preconditioner failures {stats["precond_failed"]}, '
           f'chi2 {stats["chi2"]:.6g}, |grad| {g0:.3g} -> {g1:.3g}, ATE {R.ate(d["poses"], d["gt"]):.3f} -> {R.ate(P, d["gt"]):.3f} m', flush=True)
     assert g1 <= 1e-8 * g0
     assert R.ate(P, d['gt']) < R.ate(d['poses'], d['gt'])
