@@ -1,0 +1,285 @@
+"""TEST INFRASTRUCTURE: a plain restatement of the view-synthesis and loss kernels of cl-slam_amd/csrc/geometry.hip and
+loss.hip, one function per kernel, from the formulas the kernel headers cite (depth_pose_prediction/utils.py:34-142,
+networks/layers.py:51-137, dpp.py:986-1192; oracle/functional.py is called where it already states them).
+
+    pose_to_proj                         axis-angle / translation -> T, P = (K T)[:3]
+    positions / cells / warp / warp_fwd  disparity -> depth -> sampling position, the bilinear cell and the clip flags as
+                                         DECISIONS with their margins, the bilinear read on an imposed cell
+    photo_map / ssim_coefficients        SSIM + L1 map; d map / d window element by autograd
+    automask                             4-way min, selection, gap of the two smallest candidates
+    finalize                             the 18 loss scalars and the smoothness bookkeeping (by autograd)
+    photo_backward / warp_backward       dL / d warped, dL / d upsampled disparity and dL / dP by autograd
+    disp_backward                        dL / d disparity logit
+    pose_backward                        dL / d pose-decoder output
+
+Everything is loop-free torch evaluated in `dtype`: float64 is the reference, float32 the yardstick ("what the same
+formula loses in the kernel's own number format").  Gradients come from autograd through the restatement -- no analytic
+d depth / d (u, v), no transposed stencil: those are what is under test.  A function that depends on a decision (cell,
+clip flag, selection, SSIM clamp flag, L1 sign) accepts it as an argument and evaluates the smooth part of the formula
+on the imposed decision.  Nothing here runs on the device."""
+import torch
+import torch.nn.functional as F
+
+from oracle import functional as OF
+
+F64 = torch.float64
+X_LIMIT, Y_LIMIT = 2.5e-4, 8e-5          # fp32 resolution of a sampling position in px (tests/test_warp_positions.py)
+GAP_LIMIT = 1e-5                         # ... of the gap between the two smallest candidates (tests/test_loss_stage.py)
+
+
+# ---- pose -> matrices ---------------------------------------------------------------------------------------------------
+def pose_to_proj(pose, K, dtype=F64):
+    """pose (2B, >= 6) rows fi * B + b = [axis_angle, translation, ...], frame index 0 (= frame -1) inverted; K (B,4,4)
+    -> T (2,B,4,4), P (2,B,3,4)"""
+    B = K.shape[0]
+    pose, K = pose.to(dtype), K.to(dtype)
+    T = torch.stack([OF.transformation_from_parameters(pose[fi * B:(fi + 1) * B, None, 0:3], pose[fi * B:(fi + 1) * B, None, 3:6],
+                                                       invert=fi == 0) for fi in range(2)])
+    return T, torch.matmul(K[None], T)[:, :, :3]
+
+
+# ---- view synthesis -----------------------------------------------------------------------------------------------------
+def upsample(disp_s, H, W):
+    """(B,h,w) -> (B,H,W), F.interpolate(bilinear, align_corners=False) (dpp.py:988)"""
+    return F.interpolate(disp_s[:, None], [H, W], mode='bilinear', align_corners=False)[:, 0]
+
+
+def positions(disp_up, Kinv, P, min_depth, max_depth):
+    """disp_up (B,H,W), Kinv (B,4,4), P (2,B,3,4) in one dtype -> depth (B,H,W), the normalised sampling grid
+    (2,B,H,W,2) of layers.py:93-104, the un-normalised UNCLIPPED position ix, iy (2,B,H,W) and den (2,B,H,W)"""
+    B, H, W = disp_up.shape
+    dt = disp_up.dtype
+    depth = OF.disp_to_depth(disp_up, min_depth, max_depth)
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing='ij')
+    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W, dtype=dt)])
+    X = depth.reshape(B, 1, -1) * torch.matmul(Kinv[:, :3, :3], pix)
+    p = torch.matmul(P[..., :3], X[None]) + P[..., 3:]
+    den = p[:, :, 2] + 1e-7
+    u, v = p[:, :, 0] / den, p[:, :, 1] / den
+    grid = torch.stack([(u / (W - 1) - 0.5) * 2, (v / (H - 1) - 0.5) * 2], -1).reshape(2, B, H, W, 2)
+    ix = ((grid[..., 0] + 1) / 2) * (W - 1)
+    iy = ((grid[..., 1] + 1) / 2) * (H - 1)
+    return depth, grid, ix, iy, den.reshape(2, B, H, W)
+
+
+def cells(ix, iy, H, W):
+    """the decisions of grid_sample(border, align_corners=True) at the position (ix, iy): (x0, y0, mx, my) = floor of the
+    clipped position and `not clipped`, and the margins = distance of ix / iy to the nearest cell boundary or border"""
+    ix, iy = ix.detach(), iy.detach()
+    mx, my = (ix > 0) & (ix < W - 1), (iy > 0) & (iy < H - 1)
+    x0, y0 = torch.floor(ix.clamp(0, W - 1)).long(), torch.floor(iy.clamp(0, H - 1)).long()
+    margin_x = (ix - ix.round().clamp(0, W - 1)).abs()
+    margin_y = (iy - iy.round().clamp(0, H - 1)).abs()
+    return (x0, y0, mx, my), (margin_x, margin_y)
+
+
+def unpack_cells(packed):
+    """ops.warp_cells_pyramid's x0 | y0 << 12 | (x not clipped) << 24 | (y not clipped) << 25"""
+    c = packed.long()
+    return c & 0xfff, (c >> 12) & 0xfff, ((c >> 24) & 1).bool(), ((c >> 25) & 1).bool()
+
+
+def warp(src_m1, src_p1, grid, cell):
+    """the bilinear read of the two source frames (B,3,H,W) on the imposed cells -> (2,B,3,H,W)"""
+    return torch.stack([OF.grid_sample_border(s.to(grid.dtype), grid[fi], tuple(c[fi] for c in cell)) for fi, s in enumerate((src_m1, src_p1))])
+
+
+def warp_fwd(disp_s, src_m1, src_p1, Kinv, P, H, W, min_depth, max_depth, dtype=F64, cell=None):
+    """what warp_fwd_kernel writes for one scale: depth (B,H,W), warped (2,B,3,H,W); also the decisions taken in `dtype`
+    and their margins.  cell: imposed decisions (default: this evaluation's own)."""
+    depth, grid, ix, iy, den = positions(upsample(disp_s.to(dtype), H, W), Kinv.to(dtype), P.to(dtype), min_depth, max_depth)
+    own, margins = cells(ix, iy, H, W)
+    return dict(depth=depth, warped=warp(src_m1, src_p1, grid, own if cell is None else cell), cell=own, margins=margins, den=den,
+                ix=ix, iy=iy)
+
+
+def cell_mismatch(cell_a, cell_ref, margins):
+    """pixels (any frame) where the decisions differ, and whether each such difference is a legitimate near-tie: the
+    reference margin of the axis that differs is below the fp32 resolution of the position"""
+    dx = (cell_a[0] != cell_ref[0]) | (cell_a[2] != cell_ref[2])
+    dy = (cell_a[1] != cell_ref[1]) | (cell_a[3] != cell_ref[3])
+    wrong = (dx & (margins[0] >= X_LIMIT)) | (dy & (margins[1] >= Y_LIMIT))
+    return dx | dy, wrong
+
+
+# ---- photometric map ----------------------------------------------------------------------------------------------------
+def windows(x):
+    """(N,C,H,W) -> (N,C,9,H,W): the 3x3 windows of the ReflectionPad2d(1) image (layers.py:107-137), row-major"""
+    N, C, H, W = x.shape
+    return F.unfold(F.pad(x, (1, 1, 1, 1), mode='reflect').reshape(N * C, 1, H + 2, W + 2), 3).reshape(N, C, 9, H, W)
+
+
+def _ssim_raw(mu_x, exx, exy, mu_y, eyy):
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    sig_x, sig_y, sig_xy = exx - mu_x ** 2, eyy - mu_y ** 2, exy - mu_x * mu_y
+    n = (2 * mu_x * mu_y + C1) * (2 * sig_xy + C2)
+    d = (mu_x ** 2 + mu_y ** 2 + C1) * (sig_x + sig_y + C2)
+    return (1 - n / d) / 2
+
+
+def _clamped(raw, flag):
+    """clamp(raw, 0, 1) on an imposed `inside [0, 1]` decision: raw itself where inside, a constant elsewhere"""
+    return torch.where(flag, raw, raw.detach().clamp(0, 1))
+
+
+def photo_map(pred, target, dtype=F64, flag=None, l1_sign=None):
+    """pred (N,3,H,W) against target (B,3,H,W)[n % B] (dpp.py:1178-1192) -> map (N,H,W); raw (N,3,H,W) = (1 - SSIM) / 2 before
+    the clamp with the decision flag = raw in [0, 1] and its margin; the L1 sign(target - pred) with margin |target - pred|;
+    gw (N,3,9,H,W) = d map[q] / d (window element r of pixel q), SSIM part only, by autograd."""
+    pred, target = pred.to(dtype), target.to(dtype)
+    tgt = target.repeat(pred.shape[0] // target.shape[0], 1, 1, 1)
+    xw, yw = windows(pred).requires_grad_(True), windows(tgt)
+    raw = _ssim_raw(xw.mean(2), (xw * xw).mean(2), (xw * yw).mean(2), yw.mean(2), (yw * yw).mean(2))
+    own = (raw.detach() >= 0) & (raw.detach() <= 1)
+    ssim = _clamped(raw, own if flag is None else flag)
+    diff = tgt - pred
+    sign = torch.sign(diff)
+    l1 = (sign if l1_sign is None else l1_sign.to(dtype)) * diff
+    gw, = torch.autograd.grad((0.85 / 3 * ssim).sum(), xw)
+    raw = raw.detach()
+    return dict(map=(0.85 * ssim.mean(1) + 0.15 * l1.mean(1)).detach(), raw=raw, flag=own, flag_margin=torch.minimum(raw.abs(), (raw - 1).abs()),
+                l1_sign=sign, l1_margin=diff.abs(), gw=gw)
+
+
+def ssim_coefficients(pred, target, dtype=F64, flag=None):
+    """coef (N,9,H,W), plane c * 3 + {0, 1, 2} = (alpha, beta, gamma) of channel c with
+    d map[q] / d (window element r) = alpha + beta x_r + gamma y_r.  The SSIM of a window is a function of its means
+    (E x, E x^2, E x y); autograd gives its partial derivatives with respect to those, and d E x / d x_r = 1 / 9,
+    d E x^2 / d x_r = 2 x_r / 9, d E x y / d x_r = y_r / 9."""
+    pred, target = pred.to(dtype), target.to(dtype)
+    tgt = target.repeat(pred.shape[0] // target.shape[0], 1, 1, 1)
+    xw, yw = windows(pred), windows(tgt)
+    mu, exx, exy = (v.requires_grad_(True) for v in (xw.mean(2), (xw * xw).mean(2), (xw * yw).mean(2)))
+    raw = _ssim_raw(mu, exx, exy, yw.mean(2), (yw * yw).mean(2))
+    own = (raw.detach() >= 0) & (raw.detach() <= 1)
+    g = torch.autograd.grad((0.85 / 3 * _clamped(raw, own if flag is None else flag)).sum(), [mu, exx, exy])
+    N, _, H, W = pred.shape
+    return torch.stack([g[0] / 9, 2 * g[1] / 9, g[2] / 9], 2).reshape(N, 9, H, W)
+
+
+def coef_window_gradient(coef, pred, target):
+    """alpha + beta x_r + gamma y_r for the nine window elements: (N,9,H,W) coefficients -> (N,3,9,H,W), float64"""
+    N, _, H, W = coef.shape
+    c = coef.to(F64).reshape(N, 3, 3, 1, H, W)
+    tgt = target.repeat(N // target.shape[0], 1, 1, 1)
+    return c[:, :, 0] + c[:, :, 1] * windows(pred.to(F64)) + c[:, :, 2] * windows(tgt.to(F64))
+
+
+# ---- automask -----------------------------------------------------------------------------------------------------------
+def automask(idmap, noise, rpmap, dtype=F64):
+    """idmap (2,B,H,W), noise (B,2,H,W) or None, rpmap (2,B,H,W) -> candidates (4,B,H,W), sel (B,H,W) = index of the minimum
+    (the lowest index among equals, dpp.py:1057-1058), gap = second smallest - smallest candidate"""
+    c = torch.cat([idmap.to(dtype) + (0 if noise is None else noise.to(dtype).transpose(0, 1)), rpmap.to(dtype)])
+    m, sel = c[0], torch.zeros(c.shape[1:], dtype=torch.long)
+    for k in range(1, 4):
+        lt = c[k] < m
+        m, sel = torch.where(lt, c[k], m), torch.where(lt, torch.full_like(sel, k), sel)
+    two = torch.sort(c, 0).values
+    return c, sel, two[1] - two[0]
+
+
+# ---- the loss scalars ---------------------------------------------------------------------------------------------------
+def _smooth_terms(n0, img0, n_smooth, smooth_w):
+    """the n_smooth terms of dpp.py:1148-1176 with the flattening quirk: term i = flat element i of the batch-flattened
+    gradient maps = pixel (0, i) of sample 0 (n_smooth < w - 1).  n0 (h,w) normalised disparity of sample 0, img0 (3,h,w).
+    Returns the weighted terms and the differences (dx, dy) they are functions of."""
+    dx, dy = n0[0, :n_smooth] - n0[0, 1:n_smooth + 1], n0[0, :n_smooth] - n0[1, :n_smooth]
+    ex = torch.exp(-(img0[:, 0, :n_smooth] - img0[:, 0, 1:n_smooth + 1]).abs().mean(0))
+    ey = torch.exp(-(img0[:, 0, :n_smooth] - img0[:, 1, :n_smooth]).abs().mean(0))
+    return dx, dy, lambda a, b: (a.abs() * ex + b.abs() * ey) * smooth_w
+
+
+def finalize(partials, disps, rgb0s, means, pose, dist0, dist1, sample_w, smooth_w, H, W, n_smooth, smooth_scale, vel_scale, dtype=F64):
+    """what loss_finalize_kernel writes: losses (18) = per scale (reprojection, smooth, reg, depth), velocity, total; aux
+    (4, 2 + 2 n_smooth) = per scale [1 / (mean_0 + 1e-7), fb, gxs[i], gys[i]] with, for L_s = smooth_scale / 2^s / 4 * smooth_s:
+    gxs[i] = dL_s / d dx_i, gys[i] = dL_s / d dy_i (dx, dy the differences of the normalised disparity the term i is the
+    absolute value of) and fb = -(dL_s / d mean_0) / (h w), each by autograd.
+    partials[s] (B,nblk) block sums of the minimum map, means[s] (B,chunks) chunk sums of the disparity."""
+    B = sample_w.shape[0]
+    sw = sample_w.to(dtype)
+    losses = torch.zeros(18, dtype=dtype)
+    aux = torch.zeros(4, 2 + 2 * n_smooth, dtype=dtype)
+    total = 0
+    for s in range(4):
+        h, w = disps[s].shape[-2:]
+        rl = ((partials[s].to(dtype).sum(1) / (H * W)) * sw).sum()
+        sm = torch.zeros((), dtype=dtype)
+        if n_smooth:
+            d0, img0 = disps[s][0].to(dtype), rgb0s[s][0].to(dtype)
+            m0 = (means[s][0].to(dtype).sum() / (h * w)).requires_grad_(True)
+            dx, dy, term = _smooth_terms(d0 / (m0 + 1e-7), img0, n_smooth, smooth_w.to(dtype))
+            sm = term(dx, dy).sum()
+            coefs = smooth_scale / 2 ** s / 4
+            gm, = torch.autograd.grad(coefs * sm, m0)
+            dxl, dyl = dx.detach().requires_grad_(True), dy.detach().requires_grad_(True)
+            gx, gy = torch.autograd.grad(coefs * term(dxl, dyl).sum(), [dxl, dyl])
+            aux[s, 0], aux[s, 1], aux[s, 2:2 + n_smooth], aux[s, 2 + n_smooth:] = 1 / (m0.detach() + 1e-7), -gm / (h * w), gx, gy
+            sm = sm.detach()
+        reg = smooth_scale / 2 ** s * sm
+        losses[4 * s:4 * s + 4] = torch.stack([rl, sm, reg, rl + reg])
+        total = total + rl + reg
+    total = total / 4
+    if vel_scale and vel_scale > 0:
+        p = pose.to(dtype)
+        vel = (vel_scale * OF.velocity_loss(p[:B, 3:6], p[B:2 * B, 3:6], dist0, dist1).to(dtype) * sw).sum()
+        losses[16] = vel
+        total = total + vel
+    losses[17] = total
+    return losses, aux
+
+
+# ---- backward -----------------------------------------------------------------------------------------------------------
+def photo_backward(sel, coef_sel, warped, target, sample_w, dtype=F64):
+    """dL / d warped (2,B,3,H,W) for one scale, L = sum_b sample_w[b] / (H W) / 4 * sum_q [sel[b,q] == 2 + fi] map_fi[q].
+    coef_sel (B,9,H,W) holds the SSIM derivative of the selected frame (ssim_coefficients), sel (B,H,W) the selection, both
+    INPUTS: the SSIM part of L is linearised as sum_q sum_{r in window q} (alpha_q + beta_q x_r + gamma_q y_r) x'_r with x, y
+    the given images and x' the image the gradient is taken with respect to; autograd through the padded windows does the
+    transposition.  The L1 sign is sign(warped - target) of the given images (exact: they are inputs)."""
+    B, _, H, W = target.shape
+    wv, tg, cf = warped.to(dtype), target.to(dtype), coef_sel.to(dtype).reshape(B, 3, 3, 1, H, W)
+    x = wv.clone().requires_grad_(True)
+    L = 0
+    for fi in range(2):
+        mask = (sel == 2 + fi).to(dtype)[:, None]
+        lin = cf[:, :, 0] + cf[:, :, 1] * windows(wv[fi]) + cf[:, :, 2] * windows(tg)
+        per = (mask[:, :, None] * lin * windows(x[fi])).sum((1, 2, 3, 4)) + (mask * 0.15 / 3 * torch.sign(wv[fi] - tg) * x[fi]).sum((1, 2, 3))
+        L = L + (per * sample_w.to(dtype) / (H * W) / 4).sum()
+    g, = torch.autograd.grad(L, x)
+    return g
+
+
+def warp_backward(dwarped, disp_s, src_m1, src_p1, Kinv, P, H, W, min_depth, max_depth, cell, dtype=F64):
+    """dL / d (upsampled disparity) (B,H,W) and dL / dP (2,B,3,4) of L = <dwarped, warped(disp, P)> on the imposed cells"""
+    du = upsample(disp_s.to(dtype), H, W).requires_grad_(True)
+    Pl = P.to(dtype).clone().requires_grad_(True)
+    _, grid, _, _, _ = positions(du, Kinv.to(dtype), Pl, min_depth, max_depth)
+    L = (warp(src_m1, src_p1, grid, cell) * dwarped.to(dtype)).sum()
+    return torch.autograd.grad(L, [du, Pl])
+
+
+def disp_backward(ddisp_up, disp_s, H, W, rgb0=None, smooth_w=None, smooth_scale=0.0, scale=0, dtype=F64):
+    """dL / dz (B,h,w), disp = sigmoid(z), L = <ddisp_up, upsample(disp)> + smooth_scale / 2^scale / 4 * smooth(disp / mean)"""
+    d = disp_s.to(dtype)
+    z = torch.log(d / (1 - d)).requires_grad_(True)
+    disp = torch.sigmoid(z)
+    L = (upsample(disp, H, W) * ddisp_up.to(dtype)).sum()
+    if smooth_w is not None and smooth_w.numel():
+        n = disp / (disp.mean((1, 2), keepdim=True) + 1e-7)
+        dx, dy, term = _smooth_terms(n[0], rgb0[0].to(dtype), smooth_w.numel(), smooth_w.to(dtype))
+        L = L + smooth_scale / 2 ** scale / 4 * term(dx, dy).sum()
+    g, = torch.autograd.grad(L, z)
+    return g
+
+
+def pose_backward(dp_partial, pose, K, dist0, dist1, sample_w, vel_scale, dtype=F64):
+    """dL / d pose (2B,12) of L = <sum of the partials, P(pose)> + sum_b sample_w[b] vel_scale velocity_b (dpp.py:1125-1146).
+    dp_partial (nscale,B,nblk,24), entry fi * 12 + i * 4 + j = dL / dP[fi,b,i,j]."""
+    B = K.shape[0]
+    dP = dp_partial.to(dtype).sum((0, 2)).reshape(B, 2, 3, 4).transpose(0, 1)
+    p = pose.to(dtype).clone().requires_grad_(True)
+    _, P = pose_to_proj(p, K, dtype)
+    L = (P * dP).sum()
+    if vel_scale and vel_scale > 0:
+        L = L + (vel_scale * OF.velocity_loss(p[:B, 3:6], p[B:2 * B, 3:6], dist0, dist1).to(dtype) * sample_w.to(dtype)).sum()
+    g, = torch.autograd.grad(L, p)
+    return g

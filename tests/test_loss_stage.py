@@ -90,11 +90,35 @@ def _run_loss_stage(dev, inputs, disp, pose, noise, sample_w, smooth_w, H, W, mi
     return out
 
 
+def _compute_loss(p, inputs, outputs, noise, sw, smw):
+    """the oracle's loss; with smoothness weights other than the sample weights (the kernels take the two separately, the
+    oracle one vector) the smoothness term is re-weighted: loss += sum_s 1e-3 / 2^s / 4 * ((smw - sw) . smooth_s)"""
+    losses = p.compute_loss(inputs, outputs, noise, sw)
+    if smw is sw:
+        return losses
+    total = losses['loss']
+    for s in range(4):
+        disp = outputs['disp', s]
+        norm = disp / (disp.mean(2, True).mean(3, True) + 1e-7)
+        sm = (OF.smooth_loss_reference(norm, inputs['rgb', 0, s]) * smw).sum()
+        reg = 1e-3 / 2 ** s * sm
+        total = total + (reg - losses[f'reg_loss/scale_{s}']) / 4
+        losses[f'smooth_loss/scale_{s}'], losses[f'reg_loss/scale_{s}'] = sm, reg
+        losses[f'depth_loss/scale_{s}'] = losses[f'reprojection_loss/scale_{s}'] + reg
+    losses['loss'] = total
+    return losses
+
+
 @pytest.mark.parametrize('backend', BACKENDS)
 @pytest.mark.parametrize('pyramid', [False, True])
-@pytest.mark.parametrize('B,H,W,max_depth,aligned', [(2, 32, 64, None, False), (3, 64, 128, None, True),
-                                                     (1, 32, 64, 80.0, True)])
-def test_loss_stage_matches_oracle(backend, B, H, W, max_depth, aligned, pyramid):
+@pytest.mark.parametrize('B,H,W,max_depth,aligned,weights', [
+    pytest.param(2, 32, 64, None, False, None, id='2-32-64-None-False'), pytest.param(3, 64, 128, None, True, None, id='3-64-128-None-True'),
+    pytest.param(1, 32, 64, 80.0, True, None, id='1-32-64-80.0-True'),
+    # sample weights that differ between the samples, and smoothness weights that differ from them
+    pytest.param(3, 32, 64, None, True, ((0.5, 0.3, 0.2), (0.2, 0.1, 0.7)), id='3-32-64-nonuniform-weights'),
+    # a width of 32 mod 64: the image edge inside a tile of every tiled kernel
+    pytest.param(2, 32, 96, None, True, None, id='2-32-96-None-True')])
+def test_loss_stage_matches_oracle(backend, B, H, W, max_depth, aligned, weights, pyramid):
     dev = use_backend(backend)
     torch.manual_seed(3)
     inputs = synth.make_batch(B, H, W, seed=5)
@@ -131,11 +155,13 @@ def test_loss_stage_matches_oracle(backend, B, H, W, max_depth, aligned, pyramid
         outputs['depth', s] = depth
         for f in (-1, 1):
             outputs['rgb', f, s] = warped[f]
-    sw = torch.ones(B) / B
-    losses = p.compute_loss(inputs, outputs, noise, sw)
+    sw = smw = torch.ones(B) / B
+    if weights is not None:
+        sw, smw = torch.tensor(weights[0]), torch.tensor(weights[1])
+    losses = _compute_loss(p, inputs, outputs, noise, sw, smw)
     losses['loss'].backward()
 
-    got = _run_loss_stage(dev, inputs, [outputs['disp', s].squeeze(1) for s in range(4)], pose, noise, sw, sw, H, W, 0.1,
+    got = _run_loss_stage(dev, inputs, [outputs['disp', s].squeeze(1) for s in range(4)], pose, noise, sw, smw, H, W, 0.1,
                           max_depth, pyramid=pyramid)
     for fi, f in enumerate((-1, 1)):
         assert rel_err(got['T'][fi].cpu(), Tm[f].detach()) < 1e-6
