@@ -72,6 +72,13 @@ CASES = [
     (2, 6, 20, 32, 0, 48, 3, 1, 0, False, 1, False, 22),
     (2, 12, 40, 32, 0, 64, 3, 2, 0, False, 1, False, 23),
     (1, 9, 21, 16, 0, 32, 3, 2, 0, False, 1, False, 23),
+    # configs 24 / 25: the BK = 32 variants of 22 (run tiles) and 21 (4x16 rectangles) in conv3x3_patch_dispatch
+    (2, 6, 20, 64, 0, 48, 3, 1, 0, False, 1, True, 24),      # narrow image: one 6x20 image is two 64-px runs, zero pad, residual
+    (1, 5, 22, 32, 0, 16, 3, 1, 1, False, 2, False, 24),     # reflect, a ragged last run (110 px)
+    (1, 12, 20, 16, 16, 32, 3, 1, 1, True, 2, False, 24),    # upsample + concat: ONE 32-channel chunk spans both sources
+    (2, 12, 40, 32, 0, 64, 3, 1, 0, False, 1, True, 25),     # rectangular 12x40: ragged right tiles (40 = 2 x 16 + 8)
+    (1, 10, 36, 32, 32, 32, 3, 1, 1, True, 2, False, 25),    # ragged rows and columns, upsample + concat, reflect
+    (1, 14, 44, 64, 0, 16, 3, 1, 0, False, 0, False, 25),    # zero pad, two chunks
 ]
 
 
@@ -99,6 +106,28 @@ def test_conv2d_matches_torch(case, backend):
                stride=stride, pad=pad, pad_mode=pad_mode, upsample_a=ups, act=act, config=config)
     assert rel_err(out.cpu(), ref) < 2e-5, rel_err(out.cpu(), ref)
 
+
+# Ca, Cout, stride, config: what conv3x3_patch_dispatch refuses
+REJECTED = [
+    (16, 32, 1, 24), (48, 32, 1, 24), (16, 32, 1, 25), (48, 16, 1, 25),      # BK = 32 needs Cin % 32 == 0
+    (32, 16, 1, 26), (32, 48, 1, 26),                                        # 32-channel tiles need Cout % 32 == 0
+    (32, 32, 2, 10), (32, 32, 2, 20), (32, 32, 2, 21), (32, 32, 2, 22), (32, 32, 2, 24), (32, 32, 2, 25), (32, 32, 2, 26),
+    (32, 32, 1, 23),                                                         # stride 2 is config 23's, and only its
+]
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+@pytest.mark.parametrize('case', REJECTED)
+def test_patch_dispatch_rejects(backend, case):
+    """the combinations conv3x3_patch_dispatch encodes as invalid raise with the library's message and write nothing"""
+    dev = use_backend(backend)
+    Ca, Cout, stride, config = case
+    x = torch.randn(1, 8, 16, Ca, device=dev)
+    w = torch.randn(Cout, 9, Ca, device=dev)
+    out = torch.full((1, 8 // stride, 16 // stride, Cout), float('nan'), device=dev)
+    with pytest.raises(Exception, match=r'patch configs need a 3x3 conv with stride 1 \(configs 10-22\) or 2 \(config 23\)'):
+        ops.conv2d(x, w, out, ksize=3, stride=stride, config=config)
+    assert torch.isnan(out).all()
 
 
 # B, H, W, Ca, Cb, Cout, stride, pad_mode, ups, act, resid, config
