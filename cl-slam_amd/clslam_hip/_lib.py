@@ -16,6 +16,7 @@ LIB_PATH = Path(__file__).resolve().parents[1] / 'lib' / 'libclslam_hip.so'
 OK = 0
 ACT_NONE, ACT_RELU, ACT_ELU, ACT_HSWISH, ACT_HSIGMOID = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
+DEPTH_EVAL_MEDIAN_SCALING, DEPTH_EVAL_FROM_DISP, DEPTH_EVAL_NO_MAX = 1, 2, 4
 
 fptr = C.c_void_p
 i32 = C.c_int32
@@ -150,9 +151,11 @@ _SIGNATURES = {
     'clslam_pgo_solve_workspace': [i32],
     'clslam_pgo_solve': [fptr, fptr, fptr, fptr, fptr, C.c_double, i32, C.c_double, i32, fptr, fptr, fptr, C.c_void_p],
     'clslam_pgo_update_score': [fptr, fptr, fptr, i32, fptr, fptr, fptr, fptr, fptr, i32, i32, fptr, i32, C.c_void_p],
+    'clslam_depth_metrics_scratch': [i32, i32, i32],
+    'clslam_depth_metrics': [fptr, fptr, fptr, C.c_void_p, fptr, fptr, i32, i32, i32, i32, i32, C.c_float, C.c_float, i32, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
-ABI_VERSION = 104          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
+ABI_VERSION = 105          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32]}      # return size_t
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}

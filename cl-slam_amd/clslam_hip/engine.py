@@ -1573,6 +1573,11 @@ class Engine:
             self._main = main
         return {('disp', s): st.disp[s].unsqueeze(1).clone() for s in range(3, -1, -1)}
 
+    def run_depth(self, x: torch.Tensor) -> torch.Tensor:
+        """The depth network alone (dpp.py:548-549 predict_from_image; dpp.py:402 inside compute_depth_error): depth encoder ->
+        depth decoder, no pose net, no warp, no loss.  -> ('disp', 0), (N,1,H,W)."""
+        return self.run_depth_decoder(self.run_encoder('depth_encoder', x))['disp', 0]
+
     def run_pose_decoder(self, last_features):
         """models['pose_decoder']([features]) (dpp.py:957-965; networks/pose_decoder.py:37-54): (axis_angle, translation), each
         (N, 2, 1, 3), from the last feature map of ONE pose-encoder pass."""

@@ -695,3 +695,42 @@ def pgo_solve(H, rptr, col, tri, b, lam, na, tol, max_iter, delta, work, scal, s
 def pgo_update_score(est, trial, act, nv, delta, edge_v, meas, info, huber, ne, robust, scal, out_index, stream):
     _lib.get_lib().call('clslam_pgo_update_score', _pd(est), _pd(trial), _pi(act), nv, _pd(delta), _pi(edge_v), _pd(meas), _pd(info),
                         _pd(huber), ne, int(robust), _pd(scal), int(out_index), stream)
+
+
+# ---- depth-error metrics (csrc/depth_eval.hip; the evaluator's API is clslam_hip/depth_eval.py) ----------------------------
+def depth_metrics_scratch(n: int, hg: int, wg: int) -> int:
+    return _query('clslam_depth_metrics_scratch', n, hg, wg)
+
+
+def depth_metrics(pred, gt, min_depth, max_depth, median_scaling=True, from_disp=False, out=None, resampled=None, medians=None):
+    """pred (N,h,w) depth (from_disp: sigmoid disparity), gt (N,Hg,Wg) -> (N,10) device tensor
+    [abs_diff, abs_rel, sq_rel, a1, a2, a3, rmse, rmse_log, ratio, n] (slam/utils.py:389-442); max_depth None = no upper bound.
+    resampled (N,Hg,Wg) / medians (N,2): optional extra outputs (the resampled prediction, [median gt, median pred])."""
+    for name, t in (('pred', pred), ('gt', gt)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise _lib.ClslamError(f'depth_metrics: {name} must be a (N, rows, cols) tensor, got '
+                                   f'{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}')
+    N, (h, w), (hg, wg) = pred.shape[0], pred.shape[1:], gt.shape[1:]
+    if gt.shape[0] != N or gt.device != pred.device:
+        raise _lib.ClslamError(f'depth_metrics: pred {tuple(pred.shape)} on {pred.device} and gt {tuple(gt.shape)} on {gt.device} '
+                               'must hold the same number of images on one device')
+    if min_depth is None:
+        raise _lib.ClslamError('depth_metrics: min_depth is required (the mask is gt > min_depth)')
+    if out is None:
+        out = torch.empty(N, 10, device=pred.device)
+    for name, t, shape in (('out', out, (N, 10)), ('resampled', resampled, (N, hg, wg)), ('medians', medians, (N, 2))):
+        if t is not None and tuple(t.shape) != shape:
+            raise _lib.ClslamError(f'depth_metrics: {name} must be {shape}, got {tuple(t.shape)}')
+    if N == 0:
+        return out
+    if min(h, w, hg, wg) == 0:
+        raise _lib.ClslamError(f'depth_metrics: empty plane (pred {h}x{w}, gt {hg}x{wg})')
+    words = depth_metrics_scratch(N, hg, wg)
+    if words <= 0:
+        raise _lib.ClslamError(f'depth_metrics: {N} planes of {hg}x{wg} are beyond the kernel\'s range (2^24 pixels per plane)')
+    scratch = torch.empty((words + 1) // 2, dtype=torch.float64, device=pred.device)
+    flags = ((_lib.DEPTH_EVAL_MEDIAN_SCALING if median_scaling else 0) | (_lib.DEPTH_EVAL_FROM_DISP if from_disp else 0)
+             | (_lib.DEPTH_EVAL_NO_MAX if max_depth is None else 0))
+    _lib.get_lib().call('clslam_depth_metrics', _p(pred), _p(gt), _p(out), _pa(scratch, torch.float64), _p(resampled), _p(medians),
+                        N, h, w, hg, wg, float(min_depth), 0.0 if max_depth is None else float(max_depth), flags, _stream(pred))
+    return out

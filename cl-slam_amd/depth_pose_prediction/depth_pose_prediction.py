@@ -12,8 +12,9 @@ min_depth, max_depth, log_path``; the caller's input dict is moved to the device
 
 What is different by design: all arithmetic runs in ``clslam_hip.engine.Engine`` (no autograd, no
 torch.nn compute); there is NO CPU path -- constructing the predictor without a GPU / without
-libclslam_hip.so raises.  Offline pre-training / evaluation / plotting (dpp.py:219-289, 321-526,
-538-626, 829-904, 1197-1267) is outside the accelerated path and not provided.
+libclslam_hip.so raises.  Provided from the evaluation side: ``compute_depth_error`` (dpp.py:344-468, the metrics on the device:
+clslam_hip/depth_eval.py) and ``predict_from_image`` (dpp.py:538-554).  Offline pre-training, the other evaluators and plotting
+(dpp.py:219-289, 321-342, 470-526, 556-626, 829-904, 1197-1267) are outside the accelerated path and not provided.
 """
 import math
 import shutil
@@ -527,6 +528,70 @@ class DepthPosePrediction:
         self.engine.pack_if_needed()
         outputs, _ = self._process_batch(batch, train=False)
         return outputs
+
+    def _predict_disparity_only(self, image: Tensor) -> Tensor:
+        """('disp', 0) of the depth network alone, (N,1,H,W) on the device: what predict_from_image and compute_depth_error share"""
+        self._set_eval()
+        self.engine.pack_if_needed()
+        if len(image.shape) == 3:
+            image = image.unsqueeze(dim=0)
+        return self.engine.run_depth(image.to(self.device))
+
+    def predict_from_image(self, image: Tensor, as_numpy: bool = True):
+        """Take one image as input and return the predicted depth (dpp.py:538-554)"""
+        if not self.is_trained:
+            warnings.warn('The model has not been trained yet.', RuntimeWarning)
+        from depth_pose_prediction.utils import disp_to_depth
+        depth = disp_to_depth(self._predict_disparity_only(image), self.min_depth, self.max_depth)
+        if as_numpy:
+            depth = depth.squeeze().cpu().detach().numpy()
+        return depth
+
+    def compute_depth_error(self, median_scaling: bool = True, print_results: bool = True, data_loader=None) -> Dict[str, float]:
+        """dpp.py:344-468 with the metrics on the device (ops.depth_metrics).  data_loader: any iterable of sample dicts holding
+        ('rgb_aug', 0, 0) and ('depth', 0, -1) (batch size 1, like dpp.py:382-387); None builds the validation set like
+        dpp.py:362-387, which needs the reference's `datasets` package.  Per sample only the depth network runs; the (10,) results
+        stay on the device and are read back once at the end."""
+        if not self.is_trained:
+            warnings.warn('The model has not been trained yet.', RuntimeWarning)
+        from clslam_hip import ops
+        if data_loader is None:
+            if self.dataset_type not in ('Kitti', 'Cityscapes'):
+                warnings.warn(f'Unsupported dataset: {self.dataset_type}', RuntimeWarning)
+                return {}
+            import datasets      # the reference's package (datasets/kitti.py, datasets/cityscapes.py): not part of this one
+            from torch.utils.data import DataLoader
+            dataset = getattr(datasets, self.dataset_type)(self.dataset_path, self.val_set, frame_ids=[0], scales=[0],
+                                                           height=self.height, width=self.width, with_depth=True)
+            data_loader = DataLoader(dataset, batch_size=1, shuffle=False, num_workers=self.num_workers, pin_memory=True,
+                                     drop_last=True)
+            print(f'Validation samples: {len(dataset):>5}')
+        rows = []
+        for sample_i in data_loader:
+            gt = sample_i['depth', 0, -1].to(self.device, torch.float32)
+            gt = gt.reshape(-1, gt.shape[-2], gt.shape[-1]).contiguous()
+            disp = self._predict_disparity_only(sample_i['rgb_aug', 0, 0])
+            if disp.shape[0] != gt.shape[0]:
+                raise ValueError(f"('depth', 0, -1) holds {gt.shape[0]} planes for {disp.shape[0]} images")
+            rows.append(ops.depth_metrics(disp[:, 0].contiguous(), gt, self.min_depth, self.max_depth, median_scaling=median_scaling,
+                                          from_disp=True))
+        if not rows:
+            raise ValueError('compute_depth_error: the data loader is empty')
+        res = torch.cat(rows).cpu().double().numpy()          # the one read-back
+        from clslam_hip.depth_eval import KEYS
+        # dpp.py:446-468: plain averages over the samples (a sample without valid pixels makes them NaN, like np.mean of an empty
+        # array does in the reference), the median of the ratios, the std of the ratios over it
+        metrics = {k: float(res[:, i].sum() / res.shape[0]) for i, k in enumerate(KEYS)}
+        if print_results:
+            for key, value in metrics.items():
+                print(f'{key:<8}: {value:>6.3f}')
+        if median_scaling:
+            ratios = res[:, 8]
+            med = float(np.median(ratios))
+            metrics['med_scaling'] = med
+            if print_results:
+                print(f'Scaling ratios | med: {med:.3f} | std: {np.std(ratios / med):.3f}')
+        return metrics
 
     def predict_pose(
             self,

@@ -39,9 +39,10 @@ extern "C" {
 
 /* Library identification / error text (thread-local). */
 /* ABI version: 101 = clslam_conv_desc.weight_wino appended, clslam_wino_weight_*; 100 -> 101 also covers the double* dp_partial of
- * clslam_warp_bwd / clslam_pose_bwd / clslam_loss_bwd*_pyramid (round 4); 102 = clslam_conv_desc.cu_limit appended; 103 = clslam_handoff_* added; 104 = ..._pyramid_range entry points added.
+ * clslam_warp_bwd / clslam_pose_bwd / clslam_loss_bwd*_pyramid (round 4); 102 = clslam_conv_desc.cu_limit appended; 103 = clslam_handoff_* added; 104 = ..._pyramid_range entry points added;
+ * 105 = clslam_depth_metrics* added.
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 104
+#define CLSLAM_ABI_VERSION 105
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -497,6 +498,28 @@ int clslam_pgo_solve(const double* H, const int* rptr, const int* col, const int
 int clslam_pgo_update_score(const double* est, double* trial, const int* act, int nv, const double* delta, const int* edge_v,
                             const double* meas, const double* info, const double* huber_delta, int ne, int robust, double* scal,
                             int out_index, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Depth-error metrics (csrc/depth_eval.hip).  Replaces slam/utils.py:389-442 (calc_depth_error: cv2.resize, mask, np.median
+ * scaling, clamp, the eight np.mean metrics) and the same arithmetic at dpp.py:396-440 inside compute_depth_error, including
+ * disp_to_depth(disp, min_depth, None) of dpp.py:405-406 (CLSLAM_DEPTH_EVAL_FROM_DISP: every tap is min_depth / disp BEFORE
+ * the interpolation -- the reference resizes depth).
+ * pred (n,h,w), gt (n,hg,wg) fp32 planes.  Per image: the prediction is resampled at the ground-truth pixels by OpenCV's
+ * INTER_LINEAR rule for float images (source coordinate (d + 0.5) * (src / dst) - 0.5, scale in double, narrowed to float;
+ * border cells with fraction 0; horizontal pass first; an equal-size resample is the identity); mask = gt > min_depth [and
+ * gt < max_depth]; with MEDIAN_SCALING the prediction is multiplied by median(gt) / median(pred) over the masked pixels (exact
+ * order statistics, np.median's mean of the two middle elements for even counts), then clamped to [min_depth, max_depth].
+ * out (n,10) = [abs_diff, abs_rel, sq_rel, a1, a2, a3, rmse, rmse_log, ratio (1 without scaling), count of masked pixels];
+ * an image without masked pixels gets NaN in the first nine and 0.  Bitwise reproducible (no floating-point atomics).
+ * scratch: clslam_depth_metrics_scratch(n, hg, wg) 4-byte words (0 = geometry out of range: a plane is at most 2^24 pixels),
+ * 8-byte aligned, contents irrelevant.  Optional outputs for tests and tools: resampled (n,hg,wg), the resampled prediction
+ * (0 outside the mask); medians (n,2) = [median gt, median pred] (0 without scaling, NaN for an empty mask).               */
+#define CLSLAM_DEPTH_EVAL_MEDIAN_SCALING 1
+#define CLSLAM_DEPTH_EVAL_FROM_DISP 2
+#define CLSLAM_DEPTH_EVAL_NO_MAX 4 /* max_depth is None: no upper mask bound, no upper clamp */
+int clslam_depth_metrics_scratch(int n_images, int hg, int wg);
+int clslam_depth_metrics(const float* pred, const float* gt, float* out, void* scratch, float* resampled, float* medians,
+                         int n_images, int h, int w, int hg, int wg, float min_depth, float max_depth, int flags, void* stream);
 
 #ifdef __cplusplus
 }
