@@ -734,3 +734,151 @@ def depth_metrics(pred, gt, min_depth, max_depth, median_scaling=True, from_disp
     _lib.get_lib().call('clslam_depth_metrics', _p(pred), _p(gt), _p(out), _pa(scratch, torch.float64), _p(resampled), _p(medians),
                         N, h, w, hg, wg, float(min_depth), 0.0 if max_depth is None else float(max_depth), flags, _stream(pred))
     return out
+
+
+# ---- dense mapping (csrc/mapping.hip; the map's API is clslam_hip/mapping.py) -----------------------------------------------
+def _pl(t):
+    return _pa(t, torch.int64)
+
+
+def _cloud(name: str, fn: str, t) -> None:
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 6:
+        raise _lib.ClslamError(f'{fn}: {name} must be a (M, 6) tensor, got '
+                               f'{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}')
+
+
+def _segments(fn: str, points, offsets, poses):
+    """offsets (F+1) int64 and poses (F,4,4) fp64 of a cloud, on its device; offsets given on the host (a list, an array, a host
+    tensor) are checked against the cloud and uploaded, a device tensor is taken as it is (the kernels never walk past it)"""
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+        raise _lib.ClslamError(f'{fn}: poses must be a (F, 4, 4) tensor, got '
+                               f'{tuple(poses.shape) if isinstance(poses, torch.Tensor) else type(poses).__name__}')
+    F = poses.shape[0]
+    if not (isinstance(offsets, torch.Tensor) and offsets.device == points.device and offsets.device.type != 'cpu'):
+        host = torch.as_tensor(offsets)
+        if host.dim() != 1 or host.is_floating_point():
+            raise _lib.ClslamError(f'{fn}: offsets must be a one-dimensional integer sequence')
+        host = host.to(torch.int64).cpu()
+        if host.numel() == F + 1 and (int(host[0]) != 0 or int(host[-1]) != points.shape[0] or bool((host[1:] < host[:-1]).any())):
+            raise _lib.ClslamError(f'{fn}: offsets must rise from 0 to the {points.shape[0]} points of the cloud')
+        offsets = host.to(points.device)
+    if offsets.dim() != 1 or offsets.numel() != F + 1:
+        raise _lib.ClslamError(f'{fn}: {F} poses need {F + 1} offsets, got {tuple(offsets.shape)}')
+    if poses.device != points.device:
+        raise _lib.ClslamError(f'{fn}: poses on {poses.device}, the cloud on {points.device}')
+    if F == 0 and points.shape[0]:
+        raise _lib.ClslamError(f'{fn}: {points.shape[0]} points and no segment')
+    return offsets, poses
+
+
+def pcl_backproject_scratch(n: int, h: int, w: int) -> int:
+    return _query('clslam_pcl_backproject_scratch', n, h, w)
+
+
+def pcl_backproject(depth, inv_K, image, dist_threshold=float('inf'), out=None, narrow=True):
+    """depth (N,1,H,W), inv_K (N,4,4), image (N,3,H,W) fp32 -> (points (sum M,6) fp32, offsets (N+1) int64), both on the device:
+    [cam_x, cam_y, cam_z, r, g, b] of the pixels with |cam| < dist_threshold, in image and pixel order (slam/utils.py:25-38).
+    out: a (>= N*H*W, 6) buffer to write into.  With a finite threshold the number of rows is known on the device only:
+    narrow=True reads it back (8 bytes) and returns out[:sum M]; narrow=False returns the whole buffer and reads nothing."""
+    fn = 'pcl_backproject'
+    for name, t, rank in (('depth', depth, 4), ('inv_K', inv_K, 3), ('image', image, 4)):
+        if not isinstance(t, torch.Tensor) or t.dim() != rank:
+            raise _lib.ClslamError(f'{fn}: {name} must be a tensor of rank {rank}, got '
+                                   f'{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}')
+    N, H, W = depth.shape[0], depth.shape[2], depth.shape[3]
+    if depth.shape[1] != 1 or tuple(image.shape) != (N, 3, H, W) or tuple(inv_K.shape) != (N, 4, 4):
+        raise _lib.ClslamError(f'{fn}: depth (N,1,H,W), inv_K (N,4,4) and image (N,3,H,W) expected, got {tuple(depth.shape)}, '
+                               f'{tuple(inv_K.shape)}, {tuple(image.shape)}')
+    if inv_K.device != depth.device or image.device != depth.device:
+        raise _lib.ClslamError(f'{fn}: depth on {depth.device}, inv_K on {inv_K.device}, image on {image.device}')
+    thr = float(dist_threshold)
+    if thr != thr:
+        raise _lib.ClslamError(f'{fn}: dist_threshold is NaN')
+    if N and H * W == 0:
+        raise _lib.ClslamError(f'{fn}: empty plane ({H}x{W})')
+    rows = N * H * W
+    if out is None:
+        out = torch.empty(rows, 6, device=depth.device)
+    _cloud('out', fn, out)
+    if out.shape[0] < rows:
+        raise _lib.ClslamError(f'{fn}: out has room for {out.shape[0]} rows, {N} planes of {H}x{W} may give {rows}')
+    offsets = torch.empty(N + 1, dtype=torch.int64, device=depth.device)
+    if N == 0:
+        offsets.zero_()
+        return out[:0], offsets
+    words = pcl_backproject_scratch(N, H, W)
+    if words <= 0:
+        raise _lib.ClslamError(f'{fn}: {N} planes of {H}x{W} are beyond the kernel\'s range (65535 planes of 2^30 pixels)')
+    scratch = torch.empty(words, dtype=torch.int64, device=depth.device)
+    _lib.get_lib().call('clslam_pcl_backproject', _p(depth), _p(inv_K), _p(image), _p(out), _pl(offsets), _pl(scratch), N, H, W,
+                        thr, _stream(depth))
+    if not narrow:
+        return out, offsets
+    return out[:rows if thr in (float('inf'), float('-inf')) else int(offsets[-1])], offsets
+
+
+def pcl_transform(points, offsets, poses, out=None):
+    """points (M,6) fp32, offsets (F+1) int64, poses (F,4,4) fp64 -> (M,6): segment f posed by poses[f] in fp64, rounded once
+    to fp32, colours copied (slam/utils.py:76-82)"""
+    fn = 'pcl_transform'
+    _cloud('points', fn, points)
+    offsets, poses = _segments(fn, points, offsets, poses)
+    if out is None:
+        out = torch.empty_like(points)
+    _cloud('out', fn, out)
+    if out.shape != points.shape or out.device != points.device:
+        raise _lib.ClslamError(f'{fn}: out must be {tuple(points.shape)} on {points.device}')
+    M = points.shape[0]
+    if M == 0:
+        return out
+    _lib.get_lib().call('clslam_pcl_transform', _p(points), _pl(offsets), _pd(poses), _p(out), M, poses.shape[0], _stream(points))
+    return out
+
+
+def pcl_splat_scratch(rows: int, cols: int) -> int:
+    return _query('clslam_pcl_splat_scratch', rows, cols)
+
+
+def pcl_to_image(points, K, image_shape, offsets=None, poses=None, min_z=None, return_dist=False, return_index=False,
+                 max_launch_points=1 << 32):
+    """points (M,6) fp32 [, offsets (F+1) int64 + poses (F,4,4) fp64 applied on the fly], K (3,3) fp64 -> (rows,cols,3) fp32:
+    the colour of the closest point (Euclidean distance, lowest index among equals) that projects into each pixel, 0 elsewhere
+    (slam/utils.py:41-58).  Points behind the camera project mirrored, as in the reference; min_z culls z <= min_z instead.
+    return_dist / return_index add the (rows,cols) fp32 distance plane (+inf where empty) and the int64 index plane (-1).
+    A launch takes max_launch_points (at most 2^32) points; a larger cloud goes in several, merged on the device."""
+    fn = 'pcl_to_image'
+    _cloud('points', fn, points)
+    if not isinstance(K, torch.Tensor) or tuple(K.shape) != (3, 3) or K.device != points.device:
+        raise _lib.ClslamError(f'{fn}: K must be a (3, 3) tensor on {points.device}')
+    rows, cols = (int(v) for v in image_shape[:2])
+    words = pcl_splat_scratch(rows, cols) if rows > 0 and cols > 0 else 0
+    if words <= 0:
+        raise _lib.ClslamError(f'{fn}: an image of {rows}x{cols} is empty or beyond 2^28 pixels')
+    if (offsets is None) != (poses is None):
+        raise _lib.ClslamError(f'{fn}: offsets and poses go together')
+    F = 0
+    if poses is not None:
+        offsets, poses = _segments(fn, points, offsets, poses)
+        F = poses.shape[0]
+    if min_z is not None and float(min_z) != float(min_z):
+        raise _lib.ClslamError(f'{fn}: min_z is NaN')
+    if not 0 < max_launch_points <= 1 << 32:
+        raise _lib.ClslamError(f'{fn}: max_launch_points must be in 1 .. 2^32')
+    dev, M = points.device, points.shape[0]
+    image = torch.empty(rows, cols, 3, device=dev)
+    dist = torch.empty(rows, cols, device=dev) if return_dist or M > max_launch_points else None
+    index = torch.empty(rows, cols, dtype=torch.int64, device=dev) if return_index else None
+    zbuf = torch.empty(words, dtype=torch.int64, device=dev)
+    lib, stream = _lib.get_lib(), _stream(points)
+    base = 0
+    while True:
+        count = min(M - base, max_launch_points)
+        lib.call('clslam_pcl_splat', _p(points) if M else None, _pl(offsets), _pd(poses), F, _pd(K), _pl(zbuf), rows, cols, base,
+                 count, int(min_z is not None), 0.0 if min_z is None else float(min_z), 1, stream)
+        lib.call('clslam_pcl_resolve', _p(points) if M else None, _pl(zbuf), base, _p(image), _p(dist), _pl(index), rows, cols,
+                 int(base > 0), stream)
+        base += count
+        if base >= M:
+            break
+    extra = ([dist] if return_dist else []) + ([index] if return_index else [])
+    return (image, *extra) if extra else image

@@ -147,7 +147,8 @@ extern "C" int clslam_handoff_wait(void* event, void* producer_stream, void* con
 // 103: clslam_handoff_* (additive)
 // 104: clslam_*_pyramid_range (additive)
 // 105: clslam_depth_metrics* (additive)
-extern "C" int clslam_version(void) { return 105; }
+// 106: clslam_pcl_* (additive)
+extern "C" int clslam_version(void) { return 106; }
 // identity of the kernel sources this library was LINKED from (csrc/build.py passes it when it compiles this file, which it
 // does whenever any object is rebuilt): read from the loaded library, not from a file beside it
 #ifndef CLSLAM_BUILD_ID

@@ -40,9 +40,9 @@ extern "C" {
 /* Library identification / error text (thread-local). */
 /* ABI version: 101 = clslam_conv_desc.weight_wino appended, clslam_wino_weight_*; 100 -> 101 also covers the double* dp_partial of
  * clslam_warp_bwd / clslam_pose_bwd / clslam_loss_bwd*_pyramid (round 4); 102 = clslam_conv_desc.cu_limit appended; 103 = clslam_handoff_* added; 104 = ..._pyramid_range entry points added;
- * 105 = clslam_depth_metrics* added.
+ * 105 = clslam_depth_metrics* added; 106 = clslam_pcl_* added.
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 105
+#define CLSLAM_ABI_VERSION 106
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -520,6 +520,51 @@ int clslam_pgo_update_score(const double* est, double* trial, const int* act, in
 int clslam_depth_metrics_scratch(int n_images, int hg, int wg);
 int clslam_depth_metrics(const float* pred, const float* gt, float* out, void* scratch, float* resampled, float* medians,
                          int n_images, int h, int w, int hg, int wg, float min_depth, float max_depth, int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Dense mapping (csrc/mapping.hip).  A cloud is (M,6) fp32 rows [x, y, z, r, g, b], 8-byte aligned.  No floating-point atomics:
+ * two launches agree bitwise.  Every product and sum named below is rounded on its own (no fma).
+ *
+ * clslam_pcl_backproject replaces slam/utils.py:25-38 (depth_to_pcl) with BackprojectDepth.forward (layers.py:74-79) in front:
+ * depth (n,1,h,w), inv_k (n,4,4), image (n,3,h,w) fp32.  Pixel (x, y) of image i, in row-major order (meshgrid 'xy' flattened),
+ * gives cam = depth * ((inv_k[r][0] * x + inv_k[r][1] * y) + inv_k[r][2]) for r = 0..2, in fp32, and the row [cam, r, g, b].
+ * It is kept iff sqrt((cx*cx + cy*cy) + cz*cz) < dist_threshold in fp32 (utils.py:35-37; a NaN norm is dropped), or
+ * dist_threshold is infinite (np.isinf: keep all); a NaN threshold is an error.  The kept rows of all images follow each other
+ * in `points` in image and pixel order (the order-preserving compaction of the reference's boolean mask; count -> scan ->
+ * ordered write, no atomic cursor); offsets (n+1) int64 on the device: image i owns rows [offsets[i], offsets[i+1]).  `points`
+ * must have room for n*h*w rows.  scratch: clslam_pcl_backproject_scratch(n, h, w) 8-byte words (0 = out of range: 1..65535
+ * images, planes of at most 2^30 pixels), contents irrelevant.
+ *
+ * clslam_pcl_transform replaces slam/utils.py:76-82 (accumulate_pcl): segment f = rows [offsets[f], offsets[f+1]) of `points`
+ * (offsets (n_segments+1) int64, non-decreasing, offsets[n_segments] = m; empty segments allowed) is posed by poses[f] (4x4
+ * row-major fp64): xyz' = ((R0*x + R1*y) + R2*z) + t per row of the matrix, in fp64 from the fp32 coordinates, rounded once to
+ * fp32 (the reference's pcl[:, :3] @ tmat.T, float64 because the poses are); the colours are copied.  out may be `points`.
+ *
+ * clslam_pcl_splat + clslam_pcl_resolve replace slam/utils.py:41-58 (pcl_to_image: cv2.projectPoints with zero rotation,
+ * translation and distortion, restated from OpenCV's source, and the per-point Python loop).  Points [point_base, point_base +
+ * count) of `points`, count <= 2^32; with poses != NULL each is first posed as by clslam_pcl_transform (including the rounding
+ * to fp32; offsets index the whole cloud).  Then in fp64: zi = z != 0 ? 1/z : 1; u = (x*zi)*fx + cx; v = (y*zi)*fy + cy with
+ * fx = K[0], cx = K[2], fy = K[4], cy = K[5] of the 3x3 row-major fp64 K on the device; the pixel is (floor(u), floor(v)) and the
+ * point is skipped unless 0 <= floor(v) < rows and 0 <= floor(u) < cols.  Points behind the camera are projected mirrored (the
+ * reference's behaviour); has_min_z culls z <= min_z instead.  A point with a non-finite coordinate is skipped (the reference
+ * raises on int(nan)).  zbuf (rows*cols 64-bit words, clslam_pcl_splat_scratch; `clear` fills it with all-ones first) takes the
+ * minimum of (bits of (float)sqrt((x*x + y*y) + z*z)) << 32 | (index - point_base) by 64-bit integer atomicMin: the closest
+ * point by Euclidean distance (utils.py:54), the lowest index among equal distances (the strict < of :55 in loop order).
+ * clslam_pcl_resolve: image (rows,cols,3) = the winner's colour, 0 where empty (:48); optional dist (rows,cols) = its distance,
+ * +inf where empty; optional index (rows,cols) int64 = its row in `points`, -1 where empty.  merge != 0 (needs dist): the planes
+ * hold the result of earlier launches over lower indices and change only where this launch's winner is strictly closer -- how a
+ * cloud of more than 2^32 points is rendered in several launches.                                                              */
+int clslam_pcl_backproject_scratch(int n_images, int h, int w);
+int clslam_pcl_backproject(const float* depth, const float* inv_k, const float* image, float* points, long long* offsets,
+                           void* scratch, int n_images, int h, int w, float dist_threshold, void* stream);
+int clslam_pcl_transform(const float* points, const long long* offsets, const double* poses, float* out, long long m,
+                         int n_segments, void* stream);
+int clslam_pcl_splat_scratch(int rows, int cols);
+int clslam_pcl_splat(const float* points, const long long* offsets, const double* poses, int n_segments, const double* K,
+                     unsigned long long* zbuf, int rows, int cols, long long point_base, long long count, int has_min_z,
+                     double min_z, int clear, void* stream);
+int clslam_pcl_resolve(const float* points, const unsigned long long* zbuf, long long point_base, float* image, float* dist,
+                       long long* index, int rows, int cols, int merge, void* stream);
 
 #ifdef __cplusplus
 }
