@@ -16,6 +16,7 @@ no torch.nn compute: torch supplies device memory, streams and torch.distributed
 Reference call graph being replaced: dpp.py:906-923 (_process_batch), :925-974, :976-1017,
 :1019-1120, and dpp.py:309-313 (zero_grad / backward / optimizer.step).
 """
+import contextlib
 import math
 import os
 from types import SimpleNamespace
@@ -31,6 +32,10 @@ NUM_CH_DEC = (16, 32, 64, 128, 256)
 BN_EPS = 1e-5
 
 LOSS_NAMES = ('reprojection_loss', 'smooth_loss', 'reg_loss', 'depth_loss')
+
+# blocks a weight-gradient launch is split into, two per CU: 256 / 128 would halve / quarter the 220 MB of split partials but
+# measured 3.38 / 3.44 ms per step against 3.34 (the wgrad launches become the tail of the backward)
+WGRAD_TARGET_BLOCKS = 512
 
 
 def _align4(n: int) -> int:
@@ -101,9 +106,7 @@ def _device_streams(device) -> Dict[str, Any]:
     key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
     pool = _STREAM_POOL.get(key)
     if pool is None:
-        # CLSLAM_PRIO_<NAME> = -1 (high) / 0 / 1 (low): HIP queue priority of a stream (experiments, profiles/r05_stream_priority.txt)
-        pool = {name: torch.cuda.Stream(device=device, priority=int(os.environ.get('CLSLAM_PRIO_' + name.upper(), '0')))
-                for name in ('main', 'side', 'wg', 'tail', 'capture')}
+        pool = {name: torch.cuda.Stream(device=device, priority=0) for name in ('main', 'side', 'wg', 'tail', 'capture')}
         _STREAM_POOL[key] = pool
     return pool
 
@@ -147,20 +150,13 @@ class Engine:
         self._tracked = None
         self._modules_stale = False
         self.fresh_outputs = True
-        # the depth net and the pose net are independent until the loss stage (and their backward passes
-        # after it): run the pose branch on a second HIP stream so its small 6x20 layers fill the CUs the
-        # depth branch leaves idle at kernel tails
-        # (the streams are shared by every engine of the process on this device: HIP spreads streams over four hardware
-        # queues, and a third predictor's twelfth stream lands on the queue of its own main stream -- 3.84 instead of
-        # 3.33 ms per step measured with three predictors alive)
+        # The streams are shared by every engine of the process on this device (HIP spreads a process's streams over four
+        # hardware queues: 3.84 instead of 3.33 ms per step with three predictors' private streams).
         pool = _device_streams(device)
-        # The engine's own in-order compute stream.  A training adapt() runs there: forward, backward and the optimizer step
-        # are enqueued behind each other, the CALLER's stream is only ordered behind the forward and the first three launches
-        # of the backward (`inputs_released`: the last reads of the caller's minibatch and of the output planes), so what the
-        # reference's callers do next -- outputs['cam_T_cam', 0, 1][0].cpu(), losses[k].cpu() (slam.py:181-188) -- returns
-        # while the rest of the backward + Adam keep the GPU busy; whatever touches trainable state or the workspace
-        # afterwards is ordered behind the step by wait_training().  CLSLAM_DETACHED_TRAINING=0: everything on the caller's
-        # stream like rounds 1-3 (bitwise the same results, tests/test_detached_training.py).
+        # Detached training (CLSLAM_DETACHED_TRAINING=0: off, bitwise the same, tests/test_detached_training.py): a training
+        # adapt() runs on the engine's own stream; the caller's stream is ordered behind the forward and the first three launches
+        # of the backward only (`inputs_released`), so its read-backs return while the rest of the step keeps the GPU busy.
+        # Whatever touches trainable state or the workspace afterwards goes through wait_training().  DESIGN.md "Round 4".
         self.main_stream = pool.get('main')
         self.detached_training = os.environ.get('CLSLAM_DETACHED_TRAINING', '1') != '0'
         self._train_done = None       # event: the last detached training step (incl. its optimizer step) has completed
@@ -168,6 +164,10 @@ class Engine:
         self.inputs_released = None
         self._prealloc = None         # output planes allocated by the caller's stream for the call's last forward (prealloc_outputs)
         self._prealloc_armed = False
+        # The pose net runs on `side_stream` beside the depth net (they are independent until the loss stage, and again in the
+        # backward); `wg_stream` takes the leaves of both passes: identity maps, disparity heads, weight gradients.
+        # CLSLAM_SIDE_STREAM=0: everything on one stream.  DESIGN.md "Schedule (host side)".
+        self.use_side_stream = os.environ.get('CLSLAM_SIDE_STREAM', '1') != '0'
         self.side_stream = pool.get('side')
         self.wg_stream = pool.get('wg')
         # split-K scratch of the small-M 3x3 convs: one zero-filled buffer per stream convs are launched on
@@ -176,43 +176,35 @@ class Engine:
         for st in (self.main_stream, self.side_stream, self.wg_stream, self.capture_stream):
             if st is not None:
                 self._conv_workspace(st.cuda_stream)
-        # Asynchronous tail (data-parallel mode): gradient reduction + all-reduce + Adam of step N run on their own
-        # stream; the caller's stream does not wait for them, so the frozen encoders of step N+1 overlap the
-        # xGMI all-reduce.  Whatever reads trainable state waits on the event (wait_training()).
+        # Asynchronous tail (data-parallel mode): gradient reduction + all-reduce + Adam of step N run on `tail_stream` and the
+        # caller's stream does not wait for them, so the frozen encoders of step N+1 overlap the xGMI all-reduce.  Whatever
+        # reads trainable state waits on the event (wait_training()).
         self.async_tail = False
         self.data_parallel = False    # set by DepthPosePrediction.enable_data_parallel: an all-reduce sits between reduction and Adam
-        # single-GPU path, opt-in (CLSLAM_FUSE_ADAM=1): the gradient reduction and the optimizer step as ONE launch
-        # (clslam_reduce_multi_adam; backward(defer_reduce=True) leaves the reduction to adam()).  Bitwise the two launches
-        # (tests/test_adam.py) but not faster on the MI355X: 3.316 vs 3.311 ms at B = 5, 1.515 vs 1.454 ms at K = 0 -- in the
-        # reduction only one lane in KL (4...64 for the many-split layers) holds a finished sum, so the update's six arena
-        # accesses per element run at a fraction of the Adam kernel's width; the launch saved is worth less than that.
+        self.tail_stream = pool.get('tail')
+        self._tail_event = None       # optimizer step in flight on tail_stream
+        self._tail_open = False       # backward() left its reduction on tail_stream; adam() closes it
+        # CLSLAM_FUSE_ADAM=1 (opt-in, single GPU): gradient reduction + optimizer step as ONE launch (clslam_reduce_multi_adam;
+        # backward(defer_reduce=True) leaves the reduction to adam()).  Bitwise the two launches (tests/test_adam.py), not faster:
+        # 3.316 vs 3.311 ms at B = 5, 1.515 vs 1.454 ms at K = 0 (DESIGN.md "Round 3").
         self.fuse_adam = os.environ.get('CLSLAM_FUSE_ADAM', '0') == '1'
-        # slam.py:143-147 runs models['depth_encoder'](online_image) on every frame BEFORE adapt() /
-        # adapt(online, None), whose own depth-encoder pass over the online sample repeats exactly that computation (frozen
-        # encoder, eval-mode BatchNorm, and the online sample is not augmented: rgb_aug == rgb, datasets/utils.py:25,148-150).
-        # run_encoder() keeps its input and features; a single-triplet forward whose network input has the same CONTENT
-        # takes them instead of re-running the 22 launches of the depth encoder.
+        self._pending_reduce = None
+        # Descriptor memo: slam.py:143-147 runs models['depth_encoder'](online_image) on every frame right
+        # before adapt(), whose depth-encoder pass over the (un-augmented) online sample repeats it.  run_encoder() keeps its input
+        # and features; a single-triplet forward whose network input has the same CONTENT takes them instead of 22 launches.
         self.descriptor_memo = os.environ.get('CLSLAM_DESCRIPTOR_MEMO', '1') != '0'
         self._memo = None
         self.memo_hits = 0
-        self._pending_reduce = None
-        # Data-parallel gradient exchange in BUCKETS: the flat arena is cut into three contiguous
-        # ranges in the order their gradients complete in the backward -- the pose decoder (its short backward runs beside the
-        # depth decoder's), the depth decoder's levels 3..0 + disparity heads, and last the two 512/256-channel convolutions
-        # of level 4 (53 % of the payload: they are the END of the data-gradient chain).  Each range is reduced from its
-        # partials and all-reduced on the tail stream as soon as its last weight-gradient kernel has been enqueued, so all but
-        # the last all-reduce run underneath the rest of the backward; Adam follows once.  The sequence of collectives
-        # (three all-reduces, same slices, same order) is the same on every rank whatever its workspace / overlap state.
+        # Data-parallel gradient exchange in buckets (DESIGN.md section 6 "Round 4"): the arena is cut into
+        # contiguous ranges in the order their gradients complete in the backward (bucket_ranges()); each is reduced and
+        # all-reduced on the tail stream as soon as its last weight-gradient kernel is enqueued, Adam follows once.  The sequence
+        # of collectives is the same on every rank whatever its workspace / overlap state.
         self.grad_buckets = int(os.environ.get('CLSLAM_GRAD_BUCKETS', '3'))
         self.grads_synced = False
         self.time_exchange = False    # bench.py --gpus N: time the bucket all-reduces (exchange_report())
         self.exchange_events: List[Any] = []
         self.exchange_main_done = None
-        self.tail_stream = pool.get('tail')
-        self._tail_event = None       # optimizer step in flight on tail_stream
-        self._tail_open = False       # backward() left its reduction on tail_stream; adam() closes it
         self._capturing = False
-        self.depth_first = os.environ.get('CLSLAM_DEPTH_FIRST', '1') != '0'
         # tie-break noise drawn in the loss kernel (Philox): keyed by the seed of torch's generator of this device, re-read on
         # every forward -- torch.manual_seed() after construction re-keys the stream and restarts its draw counter, like the
         # global generator the reference draws from (dpp.py:1055-1056).  noise_stream = the data-parallel shard offset: ranks
@@ -221,30 +213,11 @@ class Engine:
         self.noise_seed = 1
         self.noise_draws = 0
         self.noise_stream = 0
-        self.use_side_stream = os.environ.get('CLSLAM_SIDE_STREAM', '1') != '0'
-        # Releasing a side stream behind a launch of the dependency chain: torch.cuda.Event().record(main) puts a marker packet
-        # between two kernels of the chain (+5.0 us on the producer per hand-off, ~17 per step); an event that is the producing
-        # launch's own completion signal costs +1.3 us (tools/micro/event_gap.hip, profiles/r05_micro_calibration.txt).
-        # CLSLAM_HANDOFF=0: the recorded events of rounds 1-4.
-        self._handoff = (ops.Handoff() if (device.type == 'cuda' and os.environ.get('CLSLAM_HANDOFF', '1') != '0') else None)
-        # clslam_conv_desc.cu_limit of the persistent (stream-K / Winograd) conv launches.  The depth and the pose network of a
-        # step run on two streams; a persistent launch that takes every CU (140 KB of LDS each) shuts the other stream out
-        # for its whole duration.  With half of the chip per launch the two branches run side by side and every workgroup
-        # walks twice the units (the prologue / hand-off / epilogue phases of a launch are paid on half of the CUs).  Measured at
-        # 192x640 (profiles/r05_cu_limit_sweep.txt): minibatch of 3 / 5 / 9 triplets -2.7 / -2.9 / -1.8 % per step; 1 triplet
-        # +4 % (one triplet does not fill the chip: latency counts, not occupancy) and 33 triplets +3.7 % (every launch is long
-        # enough to fill it alone) -- hence the band.  CLSLAM_CU_LIMIT=<n> forces a value (0: the whole chip).
-        self.cu_limit_env = os.environ.get('CLSLAM_CU_LIMIT')
-        self._cu_enc = self._cu_dec = self._cu_pose = self._cu_depth = 0     # set per forward(); the stand-alone callables (run_encoder, ...) take the whole chip
-        # OPT-IN experiment (CLSLAM_EARLY_LOSS=1), steps 2..S of adapt(steps=S) (decoders only): the view synthesis, photometric
-        # stage and loss backward of the COARSE scales 3, 2, 1 issued on the leaf stream as soon as their disparity head has run,
-        # beside the decoder levels that follow; only scale 0's remain between the decoder and the data-gradient chain.  The
-        # per-scale launches write bit for bit what the pyramid launch writes (tests/test_loss_stage.py, test_frozen_reuse.py with
-        # the switch on).  Measured on MI355X, 192x640, five-step frame: B = 5 9.85 -> 9.97 ms, B = 3 7.15 -> 7.28, B = 2 5.75 -> 5.86,
-        # B = 1 inside its +-20 % host noise, B = 33 +-0: the decoder's launches already fill every wave slot, the loss kernels only
-        # take turns with them and nine more launches + two more events are paid for nothing.  Off by default.
-        self.early_loss = os.environ.get('CLSLAM_EARLY_LOSS', '0') == '1'
-        self.early_loss_max_pixels = int(os.environ.get('CLSLAM_EARLY_LOSS_MAX_PIXELS', str(1 << 40)))
+        # A side stream is released behind ONE launch of the dependency chain by that launch's own completion signal (+1.3 us on
+        # the producer) instead of an event recorded behind it (+5.0 us, ~17 hand-offs per step: tools/micro/event_gap.hip,
+        # profiles/r05_micro_calibration.txt).  Graph capture and ops.PROFILE runs still record events.
+        self._handoff = ops.Handoff() if device.type == 'cuda' else None
+        self._cu_enc = self._cu_dec = self._cu_pose = self._cu_depth = 0     # cu_limit() per forward(); the stand-alone callables (run_encoder, ...) take the whole chip
         self.device_cus = (torch.cuda.get_device_properties(device).multi_processor_count if device.type == 'cuda' else 256)
         # steps 2..S of adapt(steps=S) keep the frozen encoders' features (see forward)
         self.reuse_frozen_features = os.environ.get('CLSLAM_REUSE_FROZEN', '1') != '0'
@@ -279,7 +252,6 @@ class Engine:
         """context: the launches of the block go to stream `st`.  Outside graph capture this is ops.launch_on (no change of
         torch's current stream, 0.3 us instead of 6): the blocks it wraps contain launches of clslam_hip.ops only."""
         if st is None:
-            import contextlib
             return contextlib.nullcontext()
         return torch.cuda.stream(st) if self._capturing else ops.launch_on(st)
 
@@ -287,15 +259,19 @@ class Engine:
         return (self.async_tail and self.tail_stream is not None and self.device.type == 'cuda' and not self._capturing
                 and ops.PROFILE is None)
 
+    def _side_streams(self):
+        """(side, wg): the pose branch's and the wgrad stream; None each when use_side_stream is off or there is none"""
+        return (self.side_stream, self.wg_stream) if self.use_side_stream else (None, None)
+
     def cu_limit(self, B: int, phase: str = 'encoders') -> int:
-        """phase: 'enc_pose' / 'enc_depth' (the two frozen encoders side by side: 5/8 and 3/8 of the chip), 'decoders', 'backward' (the whole
-        chip: in steps 2..S of adapt(steps=S) nothing runs beside the depth decoder's launches -- and the decoders' summation
-        order must not depend on whether the encoders ran, tests/test_frozen_reuse.py holds the reuse bitwise invisible)"""
-        env = os.environ.get('CLSLAM_CU_LIMIT_' + phase.upper())       # experiments
-        if env is not None:
-            return int(env)
-        if self.cu_limit_env is not None:
-            return int(self.cu_limit_env)
+        """clslam_conv_desc.cu_limit of the persistent (stream-K / Winograd) conv launches of a phase (0: the whole chip).  A
+        persistent launch that takes every CU shuts the other stream out for its whole duration; on disjoint shares the two
+        frozen encoders run side by side.  Measured at 192x640 (profiles/r05_cu_limit_sweep.txt): 3 / 5 / 9 triplets -2.7 / -2.9 /
+        -1.8 % per step, 1 triplet +4 % (latency counts, not occupancy), 33 triplets +3.7 % (every launch fills the chip alone)
+        -- hence the band 2 <= B <= 16.  DESIGN.md "`cu_limit` by section".
+        phase: 'enc_pose' / 'enc_depth' (5/8 and 3/8 of the chip), 'decoders', 'backward' (the whole chip: in steps 2..S of
+        adapt(steps=S) nothing runs beside the depth decoder's launches -- and the decoders' summation order must not depend
+        on whether the encoders ran, tests/test_frozen_reuse.py holds the reuse bitwise invisible)"""
         if not phase.startswith('enc'):
             return 0
         if not (self.use_side_stream and 2 <= B <= 16):
@@ -376,7 +352,6 @@ class Engine:
 
     def training_stream(self):
         """Context manager: the stream the gradient all-reduce of the step in flight belongs on."""
-        import contextlib
         return torch.cuda.stream(self.tail_stream) if self._tail_open else contextlib.nullcontext()
 
     @torch.no_grad()
@@ -471,23 +446,10 @@ class Engine:
         dev, H, W = self.device, self.H, self.W
         E = lambda *s: torch.empty(*s, device=dev)  # noqa: E731
         ws = SimpleNamespace(B=B)
-        hs = [H >> k for k in range(6)]
-        wsz = [W >> k for k in range(6)]
-
         ws.denc = self._enc_bufs(B)
         ws.penc = self._enc_bufs(2 * B)
-        # depth decoder activations: x[i][j] = output of upconv_i_j (post-ELU), NHWC
-        ws.x = {}
-        for i in range(4, -1, -1):
-            ws.x[i, 0] = E(B, hs[i + 1], wsz[i + 1], NUM_CH_DEC[i])
-            ws.x[i, 1] = E(B, hs[i], wsz[i], NUM_CH_DEC[i])
-        ws.disp = [E(B, hs[s], wsz[s]) for s in range(4)]
-        # pose decoder
-        ws.sq = E(2 * B, hs[5], wsz[5], 256)
-        ws.p0 = E(2 * B, hs[5], wsz[5], 256)
-        ws.p1 = E(2 * B, hs[5], wsz[5], 256)
-        ws.pmean = E(2 * B, 256)
-        ws.pose = E(2 * B, 12)
+        self._depth_dec_bufs(B, ws)
+        self._pose_dec_bufs(2 * B, ws)
         # loss stage
         ws.T = E(2, B, 4, 4)
         ws.P = E(2, B, 3, 4)
@@ -517,6 +479,27 @@ class Engine:
         e.ds = [None] + [E(n, hs[2 + li], wsz[2 + li], c) for li, c in ((1, 128), (2, 256), (3, 512))]
         e.y = [[E(n, hs[2 + li], wsz[2 + li], c) for _ in range(2)] for li, c in enumerate((64, 128, 256, 512))]
         return e
+
+    def _depth_dec_bufs(self, n: int, st: Optional[SimpleNamespace] = None) -> SimpleNamespace:
+        """depth-decoder activations of n images on `st`: x[i, j] = output of upconv_i_j (post-ELU, NHWC), disp[s]"""
+        st = SimpleNamespace() if st is None else st
+        H, W = self.H, self.W
+        E = lambda *s: torch.empty(*s, device=self.device)  # noqa: E731
+        st.x = {}
+        for i in range(4, -1, -1):
+            st.x[i, 0] = E(n, H >> (i + 1), W >> (i + 1), NUM_CH_DEC[i])
+            st.x[i, 1] = E(n, H >> i, W >> i, NUM_CH_DEC[i])
+        st.disp = [E(n, H >> s, W >> s) for s in range(4)]
+        return st
+
+    def _pose_dec_bufs(self, n: int, st: Optional[SimpleNamespace] = None) -> SimpleNamespace:
+        """pose-decoder activations of n images (2B inside a step) on `st`"""
+        st = SimpleNamespace() if st is None else st
+        h5, w5 = self.H >> 5, self.W >> 5
+        E = lambda *s: torch.empty(*s, device=self.device)  # noqa: E731
+        st.sq, st.p0, st.p1 = E(n, h5, w5, 256), E(n, h5, w5, 256), E(n, h5, w5, 256)
+        st.pmean, st.pose = E(n, 256), E(n, 12)
+        return st
 
     def _train_bufs(self, ws: SimpleNamespace) -> SimpleNamespace:
         if ws.train is not None:
@@ -616,15 +599,13 @@ class Engine:
             hit = self._wb_cache[prefix] = (w, b)
         return hit
 
-    def _depth_decoder(self, ws, feats: List[torch.Tensor], early=None) -> None:
-        """early: callable(scale), run on the leaf stream right behind the disparity head of scales 3, 2, 1 (forward(): the
-        coarse scales' loss stage)"""
+    def _depth_decoder(self, ws, feats: List[torch.Tensor]) -> None:
         x = feats[4]
         ops.PERSISTENT_CU_LIMIT = self._cu_dec
         # the disparity heads of scales 3..1 are leaves of the chain (only the view synthesis reads them): they go to
         # the wgrad stream, idle during the forward, instead of sitting between two convolutions of the chain
         main = self._main
-        leaf = self.wg_stream if (main is not None and self.use_side_stream and self.wg_stream is not None) else None
+        leaf = self._side_streams()[1] if main is not None else None
         forked = False
         for i in range(4, -1, -1):
             cin0 = NUM_CH_ENC[-1] if i == 4 else NUM_CH_DEC[i + 1]
@@ -651,8 +632,6 @@ class Engine:
                         leaf.wait_event(ev)
                     with self._on(leaf):
                         ops.dispconv_fwd(x, w.view(9, NUM_CH_DEC[i]), b, ws.disp[i])
-                        if early is not None:
-                            early(i)
                     forked = True
                 else:
                     ops.dispconv_fwd(x, w.view(9, NUM_CH_DEC[i]), b, ws.disp[i])
@@ -682,7 +661,6 @@ class Engine:
         eval mode there (dpp.py:308), so their features and the identity-reprojection maps are bit-for-bit
         what the previous step computed: they are kept instead of recomputed (54 % of a step's forward
         flops).  Ignored when no valid features are held."""
-        H, W = self.H, self.W
         # the caller's stream, looked up ONCE per call (torch.cuda.current_stream() costs 3 us; it was asked 30x per step)
         self._main = torch.cuda.current_stream(self.device) if self.device.type == 'cuda' else None
         self._conv_workspace(None if self._main is None else self._main.cuda_stream)
@@ -690,7 +668,32 @@ class Engine:
             # a forward on the caller's stream (predict(), adapt(online, None)) after a detached training step: the encoders
             # below overwrite workspace the backward in flight still reads
             self._main.wait_event(self._train_done)
-        if inputs_ready is not None:
+        # what the stages share: the call's arguments, the converted frames, and what the schedule leaves for the loss stage
+        c = SimpleNamespace(inputs=inputs, inputs_ready=inputs_ready, train=train, noise=noise, draw_noise=draw_noise,
+                            keep_noise=keep_noise, have_noise=False, id_ready=None)
+        self._convert_inputs(c)
+        B = c.B
+        self._cu_enc, self._cu_dec = self.cu_limit(B, 'encoders'), self.cu_limit(B, 'decoders')
+        self._cu_pose, self._cu_depth = self.cu_limit(B, 'enc_pose'), self.cu_limit(B, 'enc_depth')
+        ops.PERSISTENT_CU_LIMIT = self._cu_dec
+        ws = self.workspace(B)
+        c.reuse = bool(reuse_frozen and self.reuse_frozen_features and getattr(ws, 'frozen_valid', False))
+        ws.frozen_valid = False
+        c.memo_feats = self._memo_lookup(c.aug[0]) if (B == 1 and not c.reuse) else None
+        if train:
+            self._train_bufs(ws)
+        if self.fresh_outputs:
+            self._fresh_output_planes(ws, B)
+        self._networks(ws, c)
+        self._loss_stage(ws, c, sample_w, smooth_w)
+        ws.frozen_valid = True      # encoder features + identity maps of THESE inputs and encoder weights are held
+        return self._outputs(ws, B), ws.losses
+
+    def _convert_inputs(self, c) -> None:
+        """c.aug / c.rgb: the three frames as contiguous fp32, c.B; the kernels index with the engine's resolution, so
+        anything else is refused up front."""
+        inputs, H, W = c.inputs, self.H, self.W
+        if c.inputs_ready is not None:
             # inputs still crossing PCIe on the caller's copy stream: events (rgb_aug[0], rgb_aug[-1], rgb_aug[+1], everything
             # there).  The depth net only reads rgb_aug[0], the pose net the three rgb_aug frames; the un-augmented
             # frames are first needed by the identity maps / the loss stage.
@@ -698,15 +701,11 @@ class Engine:
             # read planes still in flight on the copy stream, so a batch that needs a conversion waits for all of it
             needs_conversion = any(inputs[k, f, 0].dtype != torch.float32 or not inputs[k, f, 0].is_contiguous()
                                    for k in ('rgb_aug', 'rgb') for f in (-1, 0, 1))
-            self._main.wait_event(inputs_ready[3 if needs_conversion else 0])
-        aug = {f: self._img(inputs['rgb_aug', f, 0]) for f in (-1, 0, 1)}
-        rgb = {f: self._img(inputs['rgb', f, 0]) for f in (-1, 0, 1)}
-        B = aug[0].shape[0]
-        self._cu_enc, self._cu_dec = self.cu_limit(B, 'encoders'), self.cu_limit(B, 'decoders')
-        self._cu_pose, self._cu_depth = self.cu_limit(B, 'enc_pose'), self.cu_limit(B, 'enc_depth')
-        ops.PERSISTENT_CU_LIMIT = self._cu_dec
-        # the kernels index with the engine's resolution: refuse anything else up front
-        for name, group in (('rgb_aug', aug), ('rgb', rgb)):
+            self._main.wait_event(c.inputs_ready[3 if needs_conversion else 0])
+        c.aug = {f: self._img(inputs['rgb_aug', f, 0]) for f in (-1, 0, 1)}
+        c.rgb = {f: self._img(inputs['rgb', f, 0]) for f in (-1, 0, 1)}
+        B = c.B = c.aug[0].shape[0]
+        for name, group in (('rgb_aug', c.aug), ('rgb', c.rgb)):
             for f, t in group.items():
                 if tuple(t.shape) != (B, 3, H, W):
                     raise ClslamError(f"('{name}', {f}, 0) must be ({B}, 3, {H}, {W}), got {tuple(t.shape)}")
@@ -717,194 +716,137 @@ class Engine:
         for k in (('camera_matrix', 0), ('inv_camera_matrix', 0)):
             if tuple(inputs[k].shape) != (B, 4, 4):
                 raise ClslamError(f'{k} must be ({B}, 4, 4), got {tuple(inputs[k].shape)}')
-        ws = self.workspace(B)
-        reuse = bool(reuse_frozen and self.reuse_frozen_features and getattr(ws, 'frozen_valid', False))
-        ws.frozen_valid = False
-        memo_feats = self._memo_lookup(aug[0]) if (B == 1 and not reuse) else None
-        if train:
-            self._train_bufs(ws)
-        if self.fresh_outputs:
-            # the reference returns fresh tensors from every call: the output planes are (cheap, cached)
-            # new allocations that the kernels write directly -- no copies
-            pre = self._prealloc if self._prealloc_armed else None
-            if pre is not None and pre[0] == B:
-                self._prealloc = None
-                # detached step: allocated by the caller's stream (prealloc_outputs) -- the blocks belong to the pool of the
-                # stream that will read and free them, so no record_stream bookkeeping is needed (it cost ~0.1 ms per step at
-                # B = 1: an event per block and free, polled by every later allocation)
-                ws.disp, ws.pose, ws.T, ws.depth, ws.warped, ws.losses = pre[1]
-            else:
-                E = lambda *s: torch.empty(*s, device=self.device)  # noqa: E731
-                ws.disp = [E(B, H >> s, W >> s) for s in range(4)]
-                ws.pose, ws.T = E(2 * B, 12), E(2, B, 4, 4)
-                ws.depth, ws.warped, ws.losses = E(4, B, H, W), E(4, 2, B, 3, H, W), E(18)
-        def identity_and_noise() -> bool:
-            """Identity reprojection maps (dpp.py:1047-1052) and the tie-break noise depend on the inputs only."""
-            if not reuse:
-                # one launch per source frame straight from the caller's planes (stacking them first cost two 7 MB copies)
-                ops.photo_map(rgb[-1], rgb[0], ws.idmap[0], None, B, B, H, W)
-                ops.photo_map(rgb[1], rgb[0], ws.idmap[1], None, B, B, H, W)
-            if noise is not None:
-                for s in range(4):
-                    ws.noise[s].copy_(noise[s])
-                return True
-            if keep_noise:                       # already copied into ws.noise by the graph driver
-                return True
-            if draw_noise and self._capturing:
-                # a captured step replays fixed kernel arguments: torch's graph-safe generator keeps the draws fresh
-                ws.noise.normal_().mul_(1e-5)  # dpp.py:1055-1056
-                return True
-            return False
 
-        # networks ---------------------------------------------------------------------------
-        side = self.side_stream if (self.use_side_stream and self.side_stream is not None) else None
-        id_ready = None
-        wg = self.wg_stream if (self.use_side_stream and self.wg_stream is not None) else None
+    def _fresh_output_planes(self, ws, B: int) -> None:
+        """The reference returns fresh tensors from every call: the output planes are (cheap, cached) new allocations that
+        the kernels write directly -- no copies."""
+        H, W = self.H, self.W
+        pre = self._prealloc if self._prealloc_armed else None
+        if pre is not None and pre[0] == B:
+            self._prealloc = None
+            # detached step: allocated by the caller's stream (prealloc_outputs) -- the blocks belong to the pool of the
+            # stream that will read and free them, so no record_stream bookkeeping is needed (it cost ~0.1 ms per step at
+            # B = 1: an event per block and free, polled by every later allocation)
+            ws.disp, ws.pose, ws.T, ws.depth, ws.warped, ws.losses = pre[1]
+        else:
+            E = lambda *s: torch.empty(*s, device=self.device)  # noqa: E731
+            ws.disp = [E(B, H >> s, W >> s) for s in range(4)]
+            ws.pose, ws.T = E(2 * B, 12), E(2, B, 4, 4)
+            ws.depth, ws.warped, ws.losses = E(4, B, H, W), E(4, 2, B, 3, H, W), E(18)
+
+    def _identity_and_noise(self, ws, c) -> bool:
+        """Identity reprojection maps (dpp.py:1047-1052) and the tie-break noise depend on the inputs only.
+        -> whether ws.noise holds this forward's noise."""
+        if not c.reuse:
+            # one launch per source frame straight from the caller's planes (stacking them first cost two 7 MB copies)
+            ops.photo_map(c.rgb[-1], c.rgb[0], ws.idmap[0], None, c.B, c.B, self.H, self.W)
+            ops.photo_map(c.rgb[1], c.rgb[0], ws.idmap[1], None, c.B, c.B, self.H, self.W)
+        if c.noise is not None:
+            for s in range(4):
+                ws.noise[s].copy_(c.noise[s])
+            return True
+        if c.keep_noise:                     # already copied into ws.noise by the graph driver
+            return True
+        if c.draw_noise and self._capturing:
+            # a captured step replays fixed kernel arguments: torch's graph-safe generator keeps the draws fresh
+            ws.noise.normal_().mul_(1e-5)  # dpp.py:1055-1056
+            return True
+        return False
+
+    def _enqueue_identity(self, ws, c, wg) -> None:
+        """_identity_and_noise() on the wgrad stream, idle during the forward; c.id_ready is recorded behind it."""
+        if c.inputs_ready is not None:
+            wg.wait_event(c.inputs_ready[3])
+        # (injected / captured noise is written by torch ops: they need torch's current stream switched)
+        with (torch.cuda.stream(wg) if (c.noise is not None or self._capturing) else ops.launch_on(wg)):
+            c.have_noise = self._identity_and_noise(ws, c)
+        c.id_ready = torch.cuda.Event()
+        c.id_ready.record(wg)
+
+    def _pose_encoder(self, ws, c, **kw) -> torch.Tensor:
+        """last feature of the pose pairs in temporal order (dpp.py:949-955): (-1, 0) and (0, +1), batched as 2B"""
+        aug, B = c.aug, c.B
+        return self._encoder(self.enc['pose_encoder'], ws.penc, 2 * B, [(aug[-1], aug[0], 0, B), (aug[0], aug[1], B, B)],
+                             waits=None if c.inputs_ready is None else c.inputs_ready[1:3], cu_limit=self._cu_pose, **kw)[4]
+
+    def _pose_branch(self, ws, c, side, ds_aux) -> torch.Tensor:
+        with self._on(side):
+            pf4 = ws.pf4 if c.reuse else self._pose_encoder(ws, c, stream=side, aux=ds_aux)
+            self.wait_training(side)      # the (frozen) encoder above does not need the optimizer step in flight
+            self._pose_decoder(ws, pf4)
+        return pf4
+
+    def _networks(self, ws, c) -> None:
+        """Depth net on the caller's stream, pose net on the side stream, input-only work on the wgrad stream."""
+        B, reuse, main = c.B, c.reuse, self._main
+        side, wg = self._side_streams()
         # the 1x1 downsample convolutions of both encoders go to the wgrad stream (idle during the forward once the identity
         # maps are out) -- for a single triplet only, where the step is a chain of dependent 5-15 us launches (K = 0, 192x640:
         # 1.454 -> 1.403 ms per frame incl. read-back).  At B = 5 the chip is throughput-bound and the six fork/join event
-        # pairs cost more than the launches they hide (3.311 -> 3.377 ms): CLSLAM_DS_AUX=1 / 0 forces it on / off.
-        ds_mode = os.environ.get('CLSLAM_DS_AUX', 'auto')
-        ds_aux = wg if ((ds_mode == '1' or (ds_mode == 'auto' and B == 1)) and not self._capturing) else None
-
-        def enqueue_identity():
-            nonlocal have_noise, id_ready
-            if inputs_ready is not None:
-                wg.wait_event(inputs_ready[3])
-            # (injected / captured noise is written by torch ops: they need torch's current stream switched)
-            with (torch.cuda.stream(wg) if (noise is not None or self._capturing) else ops.launch_on(wg)):
-                have_noise = identity_and_noise()
-            id_ready = torch.cuda.Event()
-            id_ready.record(wg)
-        have_noise = False
-        early_state = None
+        # pairs cost more than the launches they hide (3.311 -> 3.377 ms).
+        ds_aux = wg if (B == 1 and not self._capturing) else None
         # A host minibatch still crossing PCIe: the identity maps read the un-augmented frames, i.e. they wait for the WHOLE
         # upload -- and so would everything queued behind them on the wgrad stream.  With the downsample convolutions on that
         # stream (single triplets) the first stage entry of the depth encoder must not inherit that wait (ADVICE r3): the
         # identity maps then go out AFTER the networks' launches.
-        defer_identity = wg is not None and ds_aux is not None and inputs_ready is not None and not reuse
+        defer_identity = wg is not None and ds_aux is not None and c.inputs_ready is not None and not reuse
         if wg is not None:
             # the wgrad stream idles during the forward: the input-only work runs there, off the critical path
-            wg.wait_stream(self._main)
+            wg.wait_stream(main)
             if not defer_identity:
-                enqueue_identity()
+                self._enqueue_identity(ws, c, wg)
         if side is not None:
-            main = self._main
             side.wait_stream(main)
-
-            def pose_branch():
-                with self._on(side):
-                    # pose pairs in temporal order (dpp.py:949-955): (-1, 0) and (0, +1), batched as 2B
-                    pf4 = ws.pf4 if reuse else self._encoder(self.enc['pose_encoder'], ws.penc, 2 * B,
-                                                             [(aug[-1], aug[0], 0, B), (aug[0], aug[1], B, B)],
-                                                             waits=None if inputs_ready is None else inputs_ready[1:3],
-                                                             stream=side, aux=ds_aux, cu_limit=self._cu_pose)[4]
-                    self.wait_training(side)      # the (frozen) encoder above does not need the optimizer step in flight
-                    self._pose_decoder(ws, pf4)
-                    return pf4
-
-            def depth_encoder():
-                if reuse:
-                    return ws.dfeats
-                if memo_feats is not None:
-                    return memo_feats
-                return self._encoder(self.enc['depth_encoder'], ws.denc, B, [(aug[0], None, 0, B)], stream=main, aux=ds_aux,
-                                     cu_limit=self._cu_depth)
-            # the host enqueues ~50 launches per branch (~0.7 ms): the depth branch is the longer
-            # dependency chain (encoder + decoder), so its kernels go out first
-            early = (reuse and train and self.early_loss and B * H * W <= self.early_loss_max_pixels and wg is not None
-                     and not self._capturing and ops.PROFILE is None and inputs_ready is None and id_ready is not None)
-            if early:
-                # the pose decoder (short) goes out first, with the projection matrices behind it on its own stream: every scale's
-                # view synthesis waits for them only
-                K = self._mat(inputs['camera_matrix', 0])
-                Kinv = self._mat(inputs['inv_camera_matrix', 0])
-                pf4 = pose_branch()
-                with self._on(side):
-                    ops.pose_to_proj(ws.pose, K, ws.T, ws.P)
-                pose_ready = torch.cuda.Event()
-                pose_ready.record(side)
-                draw = None
-                if not have_noise and draw_noise:
-                    draw = self._next_noise_draw()       # ONE draw per forward: element index = (scale, sample, pixel)
-                waited = [False]
-                t = ws.train
-
-                def early_loss(sc):       # on the leaf (= wgrad) stream, behind dispconv_sc; the identity maps / noise sit on it too
-                    if not waited[0]:
-                        wg.wait_event(pose_ready)
-                        waited[0] = True
-                    ops.warp_fwd_pyramid(ws.disp, rgb[-1], rgb[1], Kinv, ws.P, ws.depth, ws.warped, self.min_depth, self.max_depth,
-                                         scales=(sc, 1))
-                    if draw is None:
-                        ops.photo_automask_pyramid(ws.warped, rgb[0], ws.idmap, ws.noise if have_noise else None, ws.sel, ws.coef,
-                                                   ws.partial, B, H, W, scales=(sc, 1))
-                    else:
-                        ops.photo_automask_pyramid_rng(ws.warped, rgb[0], ws.idmap, draw[0], draw[1], ws.sel, ws.coef, ws.partial,
-                                                       B, H, W, scales=(sc, 1))
-                    ops.loss_bwd2_pyramid(ws.disp, ws.sel, ws.coef, ws.warped, rgb[0], rgb[-1], rgb[1], Kinv, ws.P, sample_w,
-                                          t.ddisp_up, t.dp_partial, self.min_depth, self.max_depth, scales=(sc, 1))
-                dfeats = ws.dfeats
-                self.wait_training(main)
-                self._depth_decoder(ws, dfeats, early=early_loss)
-                early_state = SimpleNamespace(K=K, Kinv=Kinv, draw=draw)
-            elif reuse:                 # no encoders to hide the host's launches behind: the long chain goes out first
+            if reuse:                   # no encoders to hide the host's launches behind: the long chain goes out first
                 dfeats = ws.dfeats
                 self.wait_training(main)
                 self._depth_decoder(ws, dfeats)
-                pf4 = pose_branch()
-            elif self.depth_first:
-                dfeats = depth_encoder()
-                pf4 = pose_branch()
-                self.wait_training(main)
-                self._depth_decoder(ws, dfeats)
+                pf4 = self._pose_branch(ws, c, side, ds_aux)
             else:
-                pf4 = pose_branch()
-                dfeats = depth_encoder()
+                # the host enqueues ~50 launches per branch (~0.7 ms): the depth branch is the longer dependency chain
+                # (encoder + decoder), so its kernels go out first
+                dfeats = c.memo_feats if c.memo_feats is not None else self._encoder(
+                    self.enc['depth_encoder'], ws.denc, B, [(c.aug[0], None, 0, B)], stream=main, aux=ds_aux, cu_limit=self._cu_depth)
+                pf4 = self._pose_branch(ws, c, side, ds_aux)
                 self.wait_training(main)
                 self._depth_decoder(ws, dfeats)
             main.wait_stream(side)
         else:
             self.wait_training()
-            dfeats = (ws.dfeats if reuse else memo_feats if memo_feats is not None else
-                      self._encoder(self.enc['depth_encoder'], ws.denc, B, [(aug[0], None, 0, B)], cu_limit=self._cu_depth))
+            dfeats = (ws.dfeats if reuse else c.memo_feats if c.memo_feats is not None else
+                      self._encoder(self.enc['depth_encoder'], ws.denc, B, [(c.aug[0], None, 0, B)], cu_limit=self._cu_depth))
             self._depth_decoder(ws, dfeats)
-            pf4 = ws.pf4 if reuse else self._encoder(self.enc['pose_encoder'], ws.penc, 2 * B,
-                                                     [(aug[-1], aug[0], 0, B), (aug[0], aug[1], B, B)],
-                                                     waits=None if inputs_ready is None else inputs_ready[1:3],
-                                                     cu_limit=self._cu_pose)[4]
+            pf4 = ws.pf4 if reuse else self._pose_encoder(ws, c)
             self._pose_decoder(ws, pf4)
         ws.dfeats, ws.pf4 = dfeats, pf4
         if defer_identity:
-            enqueue_identity()
-        # view synthesis + loss ------------------------------------------------------------------
-        if inputs_ready is not None:
-            self._main.wait_event(inputs_ready[3])
-        # scales still to do here: all four, or scale 0 only when the coarse ones went out beside the decoder (early_state)
-        rest = (0, 4) if early_state is None else (0, 1)
-        if early_state is None:
-            K = self._mat(inputs['camera_matrix', 0])
-            Kinv = self._mat(inputs['inv_camera_matrix', 0])
-            ops.pose_to_proj(ws.pose, K, ws.T, ws.P)
+            self._enqueue_identity(ws, c, wg)
+
+    def _loss_stage(self, ws, c, sample_w: torch.Tensor, smooth_w: Optional[torch.Tensor]) -> None:
+        """View synthesis + photometric loss of the four scales -> ws.losses; ws.ctx keeps what backward() needs."""
+        inputs, rgb, B, H, W = c.inputs, c.rgb, c.B, self.H, self.W
+        if c.inputs_ready is not None:
+            self._main.wait_event(c.inputs_ready[3])
+        K = self._mat(inputs['camera_matrix', 0])
+        Kinv = self._mat(inputs['inv_camera_matrix', 0])
+        ops.pose_to_proj(ws.pose, K, ws.T, ws.P)
+        ops.warp_fwd_pyramid(ws.disp, rgb[-1], rgb[1], Kinv, ws.P, ws.depth, ws.warped, self.min_depth, self.max_depth)
+        if c.id_ready is not None:
+            self._main.wait_event(c.id_ready)
         else:
-            K, Kinv = early_state.K, early_state.Kinv
-        ops.warp_fwd_pyramid(ws.disp, rgb[-1], rgb[1], Kinv, ws.P, ws.depth, ws.warped, self.min_depth, self.max_depth, scales=rest)
-        if id_ready is not None:
-            self._main.wait_event(id_ready)
-        else:
-            have_noise = identity_and_noise()
+            c.have_noise = self._identity_and_noise(ws, c)
         # all four scales in one launch; reprojection maps stay in registers, only the selected frame's
         # SSIM coefficients are kept for the backward
-        if have_noise or not draw_noise:
-            ops.photo_automask_pyramid(ws.warped, rgb[0], ws.idmap, ws.noise if have_noise else None, ws.sel,
-                                       ws.coef if train else None, ws.partial, B, H, W, scales=rest)
+        if c.have_noise or not c.draw_noise:
+            ops.photo_automask_pyramid(ws.warped, rgb[0], ws.idmap, ws.noise if c.have_noise else None, ws.sel,
+                                       ws.coef if c.train else None, ws.partial, B, H, W)
         else:
             # dpp.py:1055-1056 draws randn * 1e-5 on the compute device every scale, every step: here inside the kernel
-            # (Philox keyed by torch's seed, one draw offset per forward) -- no noise tensor is written or read
-            seed, offset = early_state.draw if early_state is not None else self._next_noise_draw()
+            # (Philox keyed by torch's seed, one draw offset per forward: element index = (scale, sample, pixel)) -- no noise
+            # tensor is written or read
+            seed, offset = self._next_noise_draw()
             ops.photo_automask_pyramid_rng(ws.warped, rgb[0], ws.idmap, seed, offset, ws.sel,
-                                           ws.coef if train else None, ws.partial, B, H, W, scales=rest)
-        ws.loss_bwd_scales = rest       # backward(): the coarse scales' loss backward is already out
+                                           ws.coef if c.train else None, ws.partial, B, H, W)
         ops.disp_mean_pyramid(ws.disp, ws.means, H, W)
         n_smooth = 0 if (smooth_w is None or self.smooth_intended) else int(smooth_w.numel())
         if n_smooth and not (n_smooth < (W >> 3) - 1):
@@ -927,8 +869,6 @@ class Engine:
             ops.smooth_intended_finalize(ws.si_partial, ws.means, sample_w, ws.losses, ws.si_aux, B, H, W, self.smooth_scale)
         ws.ctx = SimpleNamespace(rgb=rgb, K=K, Kinv=Kinv, d0=d0, d1=d1, sample_w=sample_w, n_smooth=n_smooth,
                                  aux=aux if n_smooth else None, B=B, rgb0=rgb0)
-        ws.frozen_valid = True      # encoder features + identity maps of THESE inputs and encoder weights are held
-        return self._outputs(ws, B), ws.losses
 
     def _memo_lookup(self, x: torch.Tensor) -> Optional[List[torch.Tensor]]:
         """Features of the last run_encoder('depth_encoder', ...) call if `x` (1,3,H,W on the device, already complete on the
@@ -1019,10 +959,8 @@ class Engine:
         plan = t.plan.get(name_prefix)
         if plan is None:
             use_patch = ops.wgrad_patch_supported(desc)
-            # two blocks per CU: 256 / 128 blocks would halve / quarter the 220 MB of split partials but measured 3.38 / 3.44 ms
-            # per step against 3.34 (the wgrad launches become the tail of the backward)
-            tb = int(os.environ.get('CLSLAM_WGRAD_BLOCKS', '512'))
-            splits = ops.wgrad_patch_splits(desc, tb) if use_patch else ops.wgrad_splits(desc, tb)
+            splits = (ops.wgrad_patch_splits(desc, WGRAD_TARGET_BLOCKS) if use_patch else
+                      ops.wgrad_splits(desc, WGRAD_TARGET_BLOCKS))
             plan = SimpleNamespace(use_patch=use_patch, splits=splits, partial=torch.empty(splits * n, device=self.device),
                                    colsum=None, nb=0)
             t.items.append((plan.partial, self._slot(self._g, name_prefix + '.weight', n), n, splits))
@@ -1099,7 +1037,7 @@ class Engine:
         H, W = self.H, self.W
         feats = ws.dfeats
         self._main = torch.cuda.current_stream(self.device) if self.device.type == 'cuda' else None
-        wg = self.wg_stream if (self.use_side_stream and self.wg_stream is not None) else None
+        side, wg = self._side_streams()
         t.wt_ready = None
         if wg is None:
             self._transpose_decoder_weights(t)
@@ -1111,9 +1049,7 @@ class Engine:
             t.wt_ready.record(wg)
         # loss -> disparity logits and pose-decoder output ----------------------------------------
         ops.loss_bwd2_pyramid(ws.disp, ws.sel, ws.coef, ws.warped, c.rgb[0], c.rgb[-1], c.rgb[1], c.Kinv, ws.P, c.sample_w,
-                              t.ddisp_up, t.dp_partial, self.min_depth, self.max_depth,
-                              scales=getattr(ws, 'loss_bwd_scales', (0, 4)))
-        ws.loss_bwd_scales = (0, 4)
+                              t.ddisp_up, t.dp_partial, self.min_depth, self.max_depth)
         ops.disp_grad_pyramid(t.ddisp_up, ws.disp, c.aux if c.n_smooth else None, c.n_smooth, t.dz_disp, H, W)
         if self.smooth_intended:
             ops.smooth_intended_bwd(ws.disp, c.rgb0, ws.si_aux, c.sample_w, t.dz_disp, H, W, self.smooth_scale)
@@ -1125,7 +1061,6 @@ class Engine:
             # it may overwrite its input buffers in place or drop them at once, like after the reference's synchronous step.
             self.inputs_released = torch.cuda.Event()
             self.inputs_released.record(self._main)
-        side = self.side_stream if (self.use_side_stream and self.side_stream is not None) else None
         bucketed = allreduce is not None and self.grad_buckets > 1
         # overlapped exchange: needs the tail stream, the side / wgrad streams and the per-bucket tables of a previous backward
         overlap = (bucketed and self._use_tail() and side is not None and wg is not None
@@ -1234,7 +1169,7 @@ class Engine:
         H, W = self.H, self.W
         feats = ws.dfeats
         main = self._main
-        wg = self.wg_stream if (self.use_side_stream and self.wg_stream is not None) else None
+        side, wg = self._side_streams()
         if wg is not None:
             wg.wait_stream(main)
 
@@ -1242,7 +1177,7 @@ class Engine:
         # (largest-weight) layers only become ready at the very end, so they alternate between the wgrad stream
         # and the side stream (idle once the short pose-decoder backward is through): two wgrads in flight
         # instead of a serial tail after the dgrad chain.
-        wg_streams = [wg] if (wg is None or self.side_stream is None) else [wg, self.side_stream]
+        wg_streams = [wg] if (wg is None or side is None) else [wg, side]
         counter = [0]
 
         ho = self._handoff if (wg is not None and not self._capturing and ops.PROFILE is None) else None
@@ -1527,11 +1462,7 @@ class Engine:
         key = ('pose', n)
         st = self._ws.get(key)
         if st is None:
-            E = lambda *s: torch.empty(*s, device=self.device)  # noqa: E731
-            h5, w5 = self.H >> 5, self.W >> 5
-            st = SimpleNamespace(penc=self._enc_bufs(n), sq=E(n, h5, w5, 256), p0=E(n, h5, w5, 256), p1=E(n, h5, w5, 256),
-                                 pmean=E(n, 256), pose=E(n, 12))
-            self._ws[key] = st
+            st = self._ws[key] = self._pose_dec_bufs(n, SimpleNamespace(penc=self._enc_bufs(n)))
         self._cu_enc = self._cu_dec = 0
         feats = self._encoder(self.enc['pose_encoder'], st.penc, n, [(a, b, 0, n)])
         self._pose_decoder(st, feats[4])
@@ -1560,12 +1491,7 @@ class Engine:
         key = ('depth_decoder', n)
         st = self._ws.get(key)
         if st is None:
-            E = lambda *s: torch.empty(*s, device=self.device)  # noqa: E731
-            st = SimpleNamespace(x={}, disp=[E(n, self.H >> s, self.W >> s) for s in range(4)])
-            for i in range(4, -1, -1):
-                st.x[i, 0] = E(n, self.H >> (i + 1), self.W >> (i + 1), NUM_CH_DEC[i])
-                st.x[i, 1] = E(n, self.H >> i, self.W >> i, NUM_CH_DEC[i])
-            self._ws[key] = st
+            st = self._ws[key] = self._depth_dec_bufs(n)
         main, self._main = self._main, None          # no side-stream fork: a plain chain on the caller's stream
         try:
             self._depth_decoder(st, feats)
@@ -1595,10 +1521,7 @@ class Engine:
         key = ('pose_decoder', n)
         st = self._ws.get(key)
         if st is None:
-            E = lambda *s: torch.empty(*s, device=self.device)  # noqa: E731
-            st = SimpleNamespace(sq=E(n, want[1], want[2], 256), p0=E(n, want[1], want[2], 256), p1=E(n, want[1], want[2], 256),
-                                 pmean=E(n, 256), pose=E(n, 12))
-            self._ws[key] = st
+            st = self._ws[key] = self._pose_dec_bufs(n)
         self._pose_decoder(st, f4)
         out = st.pose.clone().view(-1, 2, 1, 6)          # the 0.01 scale is applied by the head kernel (pose_decoder.py:50)
         return out[..., :3], out[..., 3:]

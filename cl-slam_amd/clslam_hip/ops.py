@@ -179,7 +179,6 @@ PERSISTENT_CU_LIMIT = 0
 # step (75 convolutions, host-bound) pays that 75 times.  An entry is re-used only while the three tensors that can change under
 # a call site (source, weight, output) still sit where they sat; everything else of a site is fixed by construction.
 _CONV_DESC_CACHE: dict = {}
-_DESC_CACHE_ON = __import__('os').environ.get('CLSLAM_DESC_CACHE', '1') != '0'
 
 
 def conv2d(src_a, weight, out, *, src_b=None, scale=None, shift=None, residual=None, ksize=3, stride=1,
@@ -193,7 +192,7 @@ def conv2d(src_a, weight, out, *, src_b=None, scale=None, shift=None, residual=N
     allocated at the same addresses, a descriptor with another geometry; the global one serves tests and tools."""
     if cache is None:
         cache = _CONV_DESC_CACHE
-    if key is not None and PROFILE is None and _DESC_CACHE_ON:
+    if key is not None and PROFILE is None:
         ent = cache.get(key)
         if ent is not None:
             d, ref, lib = ent

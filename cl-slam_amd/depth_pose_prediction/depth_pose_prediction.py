@@ -775,7 +775,7 @@ class DepthPosePrediction:
             # the whole upload, the upload of the unread entries queued behind the whole pose encoder, and the backward behind
             # that (profiles/r06_timeline_e2e_before.txt: 1.4 ms of the 4.25 ms end-to-end frame).  Queues are pooled per
             # priority, so a high-priority stream shares its queue with none of the engine's compute streams.
-            self._copy_stream = torch.cuda.Stream(device=dev, priority=int(os.environ.get('CLSLAM_PRIO_COPY', '-1')))
+            self._copy_stream = torch.cuda.Stream(device=dev, priority=-1)
         cur = torch.cuda.current_stream(dev)
         cs = self._copy_stream
         # No cs.wait_stream(cur): the device blocks are allocated under the copy stream (its own pool in torch's caching

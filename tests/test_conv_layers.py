@@ -716,7 +716,7 @@ def test_fallbacks_of_conv2d(name, B, cfg, backend, capsys, monkeypatch):
 
 # ---- backward -------------------------------------------------------------------------------------------------------------------
 TRAINABLE = [r for r in LAYERS if r['kind'] == 'fwd' and r['net'] in ('ddec', 'pdec')]
-WGRAD_TARGET = 512          # Engine._wgrad: CLSLAM_WGRAD_BLOCKS default
+WGRAD_TARGET = 512          # clslam_hip.engine.WGRAD_TARGET_BLOCKS (Engine._wgrad)
 FROZEN_SOURCE = ('ddec.upconv_4_0', 'pdec.squeeze')     # their source is an encoder feature: the engine takes no data gradient
 
 
