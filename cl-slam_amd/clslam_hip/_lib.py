@@ -145,7 +145,8 @@ _SIGNATURES = {
     'clslam_topk_desc': [fptr, i32, i32, i32, fptr, C.c_void_p, fptr, C.c_void_p, C.c_void_p],
     'clslam_l2_normalize_rows': [fptr, i32, i32, C.c_void_p],
     'clslam_diversity_commit': [fptr, fptr, i32, C.c_void_p, i32, i32, i32, i32, C.c_float, fptr, fptr, C.c_void_p,
-                                fptr, C.c_void_p],    'clslam_pgo_edge_eval': [fptr, fptr, fptr, i32, fptr, fptr, fptr, C.c_void_p],
+                                fptr, C.c_void_p],
+    'clslam_pgo_edge_eval': [fptr, fptr, fptr, i32, fptr, fptr, fptr, C.c_void_p],
     'clslam_pgo_lin_stride': [],
     'clslam_pgo_build_system': [fptr, fptr, fptr, fptr, fptr, i32, fptr, fptr, fptr, i32, i32, fptr, fptr, fptr, fptr, C.c_void_p],
     'clslam_pgo_solve_workspace': [i32],

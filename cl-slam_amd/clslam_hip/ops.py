@@ -181,6 +181,15 @@ PERSISTENT_CU_LIMIT = 0
 _CONV_DESC_CACHE: dict = {}
 
 
+def _conv_input_geometry(src_a, src_b, ksize, pad, upsample_a):
+    """(Hi, Wi, Ca, Cb, pad) of a conv descriptor: the input size after the optional nearest-2x upsampling of source a, the
+    channels of the two sources, and the padding (default: "same", ksize // 2)"""
+    Ha, Wa, Ca = src_a.shape[1:]
+    Hi, Wi = (Ha * 2, Wa * 2) if upsample_a else (Ha, Wa)
+    Cb = 0 if src_b is None else src_b.shape[3]
+    return Hi, Wi, Ca, Cb, ksize // 2 if pad is None else pad
+
+
 def conv2d(src_a, weight, out, *, src_b=None, scale=None, shift=None, residual=None, ksize=3, stride=1,
            pad=None, pad_mode=PAD_ZERO, upsample_a=False, act=ACT_NONE, config=-1, actgrad_src=None,
            actgrad_kind=ACT_NONE, workspace=None, weight_wino=None, cu_limit=None, key=None, cache=None):
@@ -209,11 +218,7 @@ def conv2d(src_a, weight, out, *, src_b=None, scale=None, shift=None, residual=N
                     raise _lib.ClslamError(f'clslam_conv2d failed ({rc}): {lib.cdll.clslam_last_error().decode()}')
                 return out
     B, Ho, Wo, Cout = out.shape
-    Ha, Wa, Ca = src_a.shape[1:]
-    Hi, Wi = (Ha * 2, Wa * 2) if upsample_a else (Ha, Wa)
-    Cb = 0 if src_b is None else src_b.shape[3]
-    if pad is None:
-        pad = ksize // 2
+    Hi, Wi, Ca, Cb, pad = _conv_input_geometry(src_a, src_b, ksize, pad, upsample_a)
     assert weight.shape[0] == Cout and weight.numel() == Cout * ksize * ksize * (Ca + Cb), weight.shape
     stream = _stream(out)
     if workspace is None and _CONV_WORKSPACES:
@@ -240,11 +245,7 @@ def conv2d(src_a, weight, out, *, src_b=None, scale=None, shift=None, residual=N
 def conv_desc(src_a, out_shape, *, src_b=None, ksize=3, stride=1, pad=None, pad_mode=PAD_ZERO, upsample_a=False):
     """Geometry-only descriptor of a forward conv (used by wgrad)."""
     B, Ho, Wo, Cout = out_shape
-    Ha, Wa, Ca = src_a.shape[1:]
-    Hi, Wi = (Ha * 2, Wa * 2) if upsample_a else (Ha, Wa)
-    Cb = 0 if src_b is None else src_b.shape[3]
-    if pad is None:
-        pad = ksize // 2
+    Hi, Wi, Ca, Cb, pad = _conv_input_geometry(src_a, src_b, ksize, pad, upsample_a)
     return _lib.ConvDesc(_p(src_a), _p(src_b), None, None, None, None, None, B, Hi, Wi, Ca, Cb, Ho, Wo, Cout,
                          ksize, stride, pad, pad_mode, int(upsample_a), ACT_NONE, -1, None, ACT_NONE, None, 0, None, 0)
 

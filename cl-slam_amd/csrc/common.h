@@ -64,16 +64,4 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 bool profile_next_events(hipEvent_t* start, hipEvent_t* stop);
 hipEvent_t take_handoff_event();
 
-template <typename F, typename Arg>
-inline void conv_launch(F kernel, int nblk, hipStream_t stream, const Arg& k) {
-#if CLSLAM_DEVICE_BUILD
-    hipEvent_t e0, e1;
-    if (profile_next_events(&e0, &e1)) {
-        hipExtLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, stream, e0, e1, 0, k);
-        return;
-    }
-#endif
-    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, stream, k);
-}
-
 }  // namespace clslam

@@ -11,6 +11,7 @@
 //           clslam_wgrad writes per-split partials, clslam_reduce_partials sums them in order).
 //   bias  : clslam_colsum (two-stage, deterministic).
 #include "adam_dev.h"
+#include "conv_common.h"
 
 namespace clslam {
 
@@ -335,10 +336,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradK p) {
         const int ci = ci0 + tj * MF + lane % MF;
 #pragma unroll
         for (int r = 0; r < NACC; ++r) {
-            int row;
-            if constexpr (MF == 32) row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            else row = 4 * (lane >> 4) + r;
-            const int co = co0 + ti * MF + row;
+            const int co = co0 + ti * MF + acc_row<MF>(lane, r);
             out[((size_t)co * taps + tap) * Cin + ci] = acc[s][r];
         }
     }

@@ -19,26 +19,15 @@
 // buffered with one barrier per chunk; each wave owns TM x TN MFMA tiles of MF x MF
 // (v_mfma_f32_32x32x2_f32 or v_mfma_f32_16x16x4_f32).  A lane's float4 LDS read supplies four
 // consecutive k-steps (k = 4*(lane/MF)+t), so no operand shuffling is needed.
-#include "common.h"
-
-#include <type_traits>
+#include "conv_common.h"
 
 namespace clslam {
 
-struct ConvK {
-    const float* __restrict__ src_a;
-    const float* __restrict__ src_b;
-    const float* __restrict__ wgt;
-    const float* __restrict__ scale;
-    const float* __restrict__ shift;
-    const float* __restrict__ residual;
-    const float* __restrict__ actgrad_src;
-    float* __restrict__ out;
-    int actgrad_kind;
-    int B, Hi, Wi, Ca, Cb, Ho, Wo, Cout;
-    int ksize, stride, pad, pad_mode, ups, act;
+struct ConvK : ConvOperands {
+    int ksize, stride;
     int M, tilesM, tilesN, nblk;
 };
+CLSLAM_FOLLOWS_CONV_OPERANDS(ConvK, ksize)
 
 template <int BM, int BN, int BK, int MF, int WGM>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvK p) {
@@ -193,14 +182,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvK p) {
     }
 
     // ---- epilogue: BN/bias, residual, activation, NHWC store (lanes run along channels) ------
-    // Straight-line phases (operands of all elements from clamped addresses, values with the activation switch outside the
-    // element loop, then the stores back to back): see conv_patch.hip -- the element-by-element form serialised every store
-    // behind an `s_waitcnt vmcnt(0)`.
     auto element = [&](int i, int j, int r, bool& ok) -> size_t {
-        int row;
-        if constexpr (MF == 32) row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        else row = 4 * (lane >> 4) + r;
-        const int m = m0 + wm0 + i * MF + row;
+        const int m = m0 + wm0 + i * MF + acc_row<MF>(lane, r);
         const int n = n0 + wn0 + j * MF + (lane % MF);
         ok = m < p.M && n < p.Cout;
         return (size_t)min(m, p.M - 1) * p.Cout + min(n, p.Cout - 1);
@@ -212,64 +195,9 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvK p) {
         sc[j] = p.scale ? p.scale[n] : 1.f;
         sh[j] = p.shift ? p.shift[n] : 0.f;
     }
-    float resq[TM][TN][NACC], agq[TM][TN][NACC];
-    const bool has_res = p.residual != nullptr, has_ag = p.actgrad_src != nullptr;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < NACC; ++r) { resq[i][j][r] = 0.f; agq[i][j][r] = 1.f; }
-    if (has_res) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NACC; ++r) { bool ok; resq[i][j][r] = p.residual[element(i, j, r, ok)]; }
-    }
-    if (has_ag) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NACC; ++r) { bool ok; agq[i][j][r] = p.actgrad_src[element(i, j, r, ok)]; }
-    }
-    auto values = [&](auto act_tag) {
-        constexpr int ACT = decltype(act_tag)::value;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NACC; ++r) {
-                    const float v = acc[i][j][r] * sc[j] + sh[j] + resq[i][j][r];
-                    acc[i][j][r] = ACT < 0 ? apply_act(v, p.act) : apply_act(v, ACT);
-                }
-    };
-    if (p.act == CLSLAM_ACT_RELU) values(std::integral_constant<int, CLSLAM_ACT_RELU>{});
-    else if (p.act == CLSLAM_ACT_NONE) values(std::integral_constant<int, CLSLAM_ACT_NONE>{});
-    else if (p.act == CLSLAM_ACT_ELU) values(std::integral_constant<int, CLSLAM_ACT_ELU>{});
-    else values(std::integral_constant<int, -1>{});
-    if (has_ag) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NACC; ++r) acc[i][j][r] *= act_grad_from_output(agq[i][j][r], p.actgrad_kind);
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < NACC; ++r) {
-                bool ok;
-                const size_t o = element(i, j, r, ok);
-                if (ok) p.out[o] = acc[i][j][r];
-            }
+    const float no_pre_res[1] = {0.f};
+    fused_epilogue<TM, TN, NACC, false, CLSLAM_ACT_RELU, CLSLAM_ACT_NONE, CLSLAM_ACT_ELU>(
+        p, sc, sh, no_pre_res, [&](int i, int j, int r) { return acc[i][j][r]; }, element);
 }
 
 template <int BM, int BN, int BK, int MF, int WGM>
@@ -277,7 +205,7 @@ static int launch_conv(ConvK k, hipStream_t stream) {
     k.tilesM = cdiv(k.M, BM);
     k.tilesN = cdiv(k.Cout, BN);
     k.nblk = k.tilesM * k.tilesN;
-    conv_launch(conv_igemm_kernel<BM, BN, BK, MF, WGM>, k.nblk, stream, k);
+    conv_launch(conv_igemm_kernel<BM, BN, BK, MF, WGM>, k.nblk, 256, stream, k);
     return check_launch("conv_igemm");
 }
 
@@ -300,32 +228,42 @@ using namespace clslam;
 //   4: 128x16x16  16x16x4  4x1 (2x1 tiles/wave)          Cout == 16, Cin % 32 != 0
 //   5:  64x32x16  16x16x4  2x2                           BK = 16 fallback
 //   6: 128x16x32  16x16x4  4x1                           Cout == 16, Cin % 32 == 0
-//  10-13: LDS-patch kernel for 3x3 stride-1 convs (conv_patch.hip): 8x16 px x {64,32,16} ch, 4x16 px x 64 ch
-extern "C" int clslam_conv2d_pick_config(const clslam_conv_desc* d) {
+//  10-26: LDS-patch kernel for 3x3 convs (conv_patch.hip), 30-37: stream-K (conv_sk.hip), 40: Winograd (conv_wino.hip)
+//
+// The picker: four functions in the order they are tried, each returning its configuration or 0 for "not mine".
+// config == -2 asks for the tiled kernels only (tiled_config below): the two persistent ones stand back.
+
+// both sources of the K chunks of the BK = 32 tilings are multiples of 32 channels
+static bool bk32_ok(const clslam_conv_desc* d) {
+    return ((d->ch_a + d->ch_b) % 32 == 0) && (d->ch_b == 0 || d->ch_a % 32 == 0);
+}
+
+// Winograd F(2x2,3x3) (conv_wino.hip, config 40) wherever the caller supplied the transformed filter: 2.25x fewer MFMAs,
+// where a persistent workgroup gets enough (tile, stage) units to amortise the kernel's fixed costs, or the direct kernels are
+// at their weakest (the 6x20 layers): see conv3x3_wino_units_per_group.  The threshold was re-swept after the direct kernels
+// got faster (6 / 8 / 10 / 12 / 20 units: 3.075 / 3.071 / 3.137 / 3.169 / 3.105 ms per step): 8 stays.
+constexpr int kWinoMinUnits = 8;
+
+static int pick_winograd(const clslam_conv_desc* d) {
+    if (d->config == -2 || d->workspace == nullptr) return 0;       // tiled kernels only / no scratch for the hand-off
+    if (getenv("CLSLAM_NO_WINOGRAD")) return 0;
+    if (!conv3x3_wino_supported(d) || d->ch_a + d->ch_b < 64 || d->ch_out < 64) return 0;
+    const int upg = conv3x3_wino_units_per_group(d);
+    return (upg >= kWinoMinUnits || (d->out_w <= 24 && upg >= 5)) ? 40 : 0;
+}
+
+// Deep, small-M layers (the 6x20 / 12x40 stages, 256-512 channels): the persistent stream-K kernel (conv_sk.hip).
+// Measured on MI355X, B=5 / 2B=10 (profiles/r02_conv_microbench.txt): layer4 51 -> 67, layer4 (pose) 70 -> 85,
+// layer3 (pose) 80 -> 87, upconv_4_0 36 -> 50, pose decoder 46 -> 55, upconv_4_1 79 -> 86, layer4.0 (stride 2)
+// 32 -> 38 TFLOP/s.  On the short-K layers (64-128 channels) every workgroup starts and ends at the same moment and
+// the synchronized first-load / last-store bursts cost more than the even split gains: those stay on the tiled kernel.
+static int pick_stream_k(const clslam_conv_desc* d) {
+    if (d->config == -2 || d->workspace == nullptr) return 0;       // tiled kernels only / no scratch for the hand-off
+    if (getenv("CLSLAM_NO_STREAMK")) return 0;
+    if (d->ksize != 3 || d->ch_out < 64) return 0;
     const int Cin = d->ch_a + d->ch_b;
     const int M = d->batch * d->out_h * d->out_w;
-    const bool bk32 = (Cin % 32 == 0) && (d->ch_b == 0 || d->ch_a % 32 == 0);
-    // Winograd F(2x2,3x3) (conv_wino.hip, config 40) wherever the caller supplied the transformed filter: 2.25x fewer MFMAs
-    // (config 40), where a persistent workgroup gets enough (tile, stage) units to amortise the kernel's
-    // fixed costs, or the direct kernels are at their weakest (the 6x20 layers): see conv3x3_wino_units_per_group
-    if (d->config != -2 && d->workspace != nullptr && conv3x3_wino_supported(d) && Cin >= 64 && d->ch_out >= 64 && !getenv("CLSLAM_NO_WINOGRAD")) {
-        static const int min_units = getenv("CLSLAM_WINO_MIN_UNITS") ? atoi(getenv("CLSLAM_WINO_MIN_UNITS")) : 8;
-        const int upg = conv3x3_wino_units_per_group(d);
-        if (upg >= min_units || (d->out_w <= 24 && upg >= 5)) return 40;
-    }
-    // 3x3 stride-1: the LDS-patch kernel (conv_patch.hip).  Measured on MI355X (tools/bench_conv.py,
-    // B=5 @192x640): 128 px x 16 ch tiles reach 80-104 TFLOP/s on the >= 48x160 layers, 64 px x 16 ch
-    // tiles 65-95 TFLOP/s on the smaller ones, 64-px row-major runs 46-70 TFLOP/s on the 6x20 layers
-    // (a 4x16 rectangle wastes half its lanes there); all beat every conv_igemm tiling (26-67).
-    // Deep, small-M layers (the 6x20 / 12x40 stages, 256-512 channels): the persistent stream-K kernel (conv_sk.hip).
-    // Measured on MI355X, B=5 / 2B=10 (profiles/r02_conv_microbench.txt): layer4 51 -> 67, layer4 (pose) 70 -> 85,
-    // layer3 (pose) 80 -> 87, upconv_4_0 36 -> 50, pose decoder 46 -> 55, upconv_4_1 79 -> 86, layer4.0 (stride 2)
-    // 32 -> 38 TFLOP/s.  On the short-K layers (64-128 channels) every workgroup starts and ends at the same moment and
-    // the synchronized first-load / last-store bursts cost more than the even split gains: those stay on the tiled kernel.
-    const bool sk_ok = d->workspace != nullptr && d->ksize == 3 && d->ch_out >= 64 && !getenv("CLSLAM_NO_STREAMK") &&
-                       d->config != -2;          // config -2: the tiled kernels only (fallback of clslam_conv2d below)
-    static const int sk_all = getenv("CLSLAM_SK_ALL") ? atoi(getenv("CLSLAM_SK_ALL")) : 0;   // experiment knob
-    if (sk_ok && sk_all && Cin >= sk_all) return d->stride == 2 ? (d->out_w <= 44 ? 31 : 30) : (d->out_w <= 44 ? 32 : 30);
+    const int px = d->out_h * d->out_w;
     // Measured per layer shape at B = 5 and B = 1 (tools/bench_conv.py, profiles/r02d_conv_microbench*.txt).  The choice
     // between 128- and 64-pixel tiles is the number of (tile, chunk) units: fewer than five per workgroup and the smaller
     // tile's finer cut wins.  Since the owner of a tile fetches its contributors' slabs four at a time the even split also
@@ -333,26 +271,16 @@ extern "C" int clslam_conv2d_pick_config(const clslam_conv_desc* d) {
     // waves per SIMD, 120 KB of LDS), so the other two streams of the step stand still behind it; while the B <= 3 steps were
     // bound by the host's launch path that cost more than the faster kernels gained (1.60-1.76 vs 1.55 ms at B = 1) and a
     // 32-tile minimum kept stream-K off there.  With the launch path trimmed the balance flipped (B = 1: 1.29-1.33 vs
-    // 1.31-1.33 ms, B = 2 / 3 / 4: -2.8 / -2.7 / -1.7 %, B = 5: -0.4 %): no minimum any more (CLSLAM_SK_FILL=<tiles> restores one).
-    static const int sk_fill_min = getenv("CLSLAM_SK_FILL") ? atoi(getenv("CLSLAM_SK_FILL")) : 0;
-    const bool sk_fill = (long long)d->batch * cdiv(d->out_h * d->out_w, 128) * cdiv(d->ch_out, 64) >= sk_fill_min;
-    // ... and only where the pixel tiles are reasonably full: a 64-pixel run on a 2x4 image (the 64x128 test frames) is
-    // 12 % pixels and 88 % padding MFMAs (6x20 in 8x16 tiles, 47 %, still wins: 39.6 vs 32.2 TFLOP/s)
-    const int px = d->out_h * d->out_w;
-    auto full_enough = [&](int cfg) {
-        const int covered = cfg == 32 ? cdiv(px, 128) * 128 : cfg == 33 ? cdiv(px, 64) * 64
-                                      : cdiv(d->out_h, cfg == 30 ? 8 : 4) * (cfg == 30 ? 8 : 4) * cdiv(d->out_w, 16) * 16;
-        return px * 10 >= covered * 4;
-    };
+    // 1.31-1.33 ms, B = 2 / 3 / 4: -2.8 / -2.7 / -1.7 %, B = 5: -0.4 %): no minimum any more.
     int sk = 0;
-    if (sk_ok && sk_fill && d->stride == 1 && d->out_h == d->in_h + 2 * d->pad - 2 && d->out_w == d->in_w + 2 * d->pad - 2) {
+    if (same_size_3x3(d, 1)) {
         const long long units128 = (long long)d->batch * cdiv(px, 128) * cdiv(d->ch_out, 64) * (Cin / 16);
         // 256 -> 256 @12x40 at B = 5 is a tie stand-alone (74.0 tiled / 73.6) and 0.5 % slower inside the step: tiled
         const bool tie_case = Cin < 512 && d->ch_out >= 256 && d->out_w > 24 && units128 >= 1280 && M < 4000;
         if (d->out_w <= 44 && Cin >= 256 && !tie_case) sk = units128 >= 1280 ? 32 : 33;
         else if (d->out_w <= 84 && d->out_w > 44 && Cin >= 256 && M >= 4000) sk = 30;
     }
-    if (sk_ok && sk_fill && d->stride == 2 && d->out_w <= 24 && Cin >= 256) {
+    if (d->stride == 2 && d->out_w <= 24 && Cin >= 256) {
         // the last stage entry (256 -> 512, 12x40 -> 6x20): 8x16 rectangles cover a 6x20 image with 8x32 pixels (47 % real);
         // one 128-pixel stride-2 RUN covers it with 94 % (config 32 with stride 2) when its 13 x 41 input band fits the stage.
         // Measured (MI355X, tools/bench_conv.py): B = 5: 45.0 vs 37.1 TFLOP/s, 2B = 10: 66.1 vs 42.6, step 3.32 -> 3.27 ms;
@@ -360,41 +288,70 @@ extern "C" int clslam_conv2d_pick_config(const clslam_conv_desc* d) {
         const int spanned = std::min(d->out_h, (127 + d->out_w - 1) / d->out_w + 1);
         const bool band_fits = ((spanned - 1) * 2 + 3) * ((d->out_w - 1) * 2 + 3) <= 544;
         const long long units = (long long)d->batch * cdiv(px, 128) * cdiv(d->ch_out, 64) * (Cin / 16);
-        if (units >= 512) sk = (band_fits && !getenv("CLSLAM_NO_SK_RUN_S2")) ? 32 : 30;
+        if (units >= 512) sk = band_fits ? 32 : 30;
         else sk = 31;
     }
     // the pose encoder's layer2.0 (64 -> 128, stride 2, 2B images): 74.7 vs 66.2 TFLOP/s; at B = 5 (M = 9600) the tiled kernel wins
-    if (sk_ok && sk_fill && d->stride == 2 && d->out_w > 24 && d->out_w <= 84 && M >= 16000) sk = 30;
-    if (sk && full_enough(sk)) return sk;
-    if (d->ksize == 3 && d->stride == 1 && d->out_h == d->in_h + 2 * d->pad - 2 && d->out_w == d->in_w + 2 * d->pad - 2) {
-        if (d->out_w <= 24) return 22;                         // narrow images: run tiles
-        // (config 26, 4x8 px x 32 ch tiles without overhang on 12x40, measured 67 vs 69 TFLOP/s for config 21: not picked)
-        // 8x16 (config 20) or 4x16 (config 21) pixel tiles.  Round 2 chose by M alone (>= 16000: 20).  Measured per shape in
-        // round 3 (tools/bench_conv.py incl. BENCH_DGRAD=1, B = 1 / 5 / 10): what decides is (a) how much of the tile grid is
-        // real pixels -- the padded dgrad domains are 14x42, 26x82, 50x162: 4-row tiles cover 50x162 with 88 % against 82 %
-        // (+8.6 %) -- and (b) whether the 8x16 grid has enough workgroups for 1280 slots: 600 of them lose 9-12 % to 1200
-        // 4x16 ones (128 -> 128 @24x80 at B = 5, 64 -> 32 @48x160, 128 -> 64 @24x80 at 2B), while on the small 14x42 domains at
-        // B >= 5 the larger tile wins by 7-11 % at equal coverage.
-        static const bool pick_v2 = !getenv("CLSLAM_PICK_V1");
-        if (pick_v2 && d->ch_out >= 32) {
-            const double cov20 = (double)px / ((double)cdiv(d->out_h, 8) * 8 * cdiv(d->out_w, 16) * 16);
-            const double cov21 = (double)px / ((double)cdiv(d->out_h, 4) * 4 * cdiv(d->out_w, 16) * 16);
-            const long long nblk20 = (long long)d->batch * cdiv(d->out_h, 8) * cdiv(d->out_w, 16) * cdiv(d->ch_out, 16);
-            if (cov21 > 1.04 * cov20) return 21;
-            if (M >= 4000) return nblk20 < 1000 ? 21 : 20;
-            return nblk20 >= 400 ? 20 : 21;
-        }
-        return M >= 16000 ? 20 : 21;                           // 20/21/22 = 12/17/18 with conflict-free LDS rows (24x80 at 2B: 91.5 vs 88.4)
+    if (d->stride == 2 && d->out_w > 24 && d->out_w <= 84 && M >= 16000) sk = 30;
+    if (!sk) return 0;
+    // ... and only where the pixel tiles are reasonably full: a 64-pixel run on a 2x4 image (the 64x128 test frames) is
+    // 12 % pixels and 88 % padding MFMAs (6x20 in 8x16 tiles, 47 %, still wins: 39.6 vs 32.2 TFLOP/s)
+    const int covered = sk == 32 ? cdiv(px, 128) * 128 : sk == 33 ? cdiv(px, 64) * 64
+                                 : cdiv(d->out_h, sk == 30 ? 8 : 4) * (sk == 30 ? 8 : 4) * cdiv(d->out_w, 16) * 16;
+    return px * 10 >= covered * 4 ? sk : 0;
+}
+
+// 3x3: the LDS-patch kernel (conv_patch.hip).  Measured on MI355X (tools/bench_conv.py, B=5 @192x640): 128 px x 16 ch tiles
+// reach 80-104 TFLOP/s on the >= 48x160 layers, 64 px x 16 ch tiles 65-95 TFLOP/s on the smaller ones, 64-px row-major runs
+// 46-70 TFLOP/s on the 6x20 layers (a 4x16 rectangle wastes half its lanes there); all beat every conv_igemm tiling (26-67).
+static int pick_patch(const clslam_conv_desc* d) {
+    if (same_size_3x3(d, 2)) return 23;
+    if (!same_size_3x3(d, 1)) return 0;
+    if (d->out_w <= 24) return 22;                         // narrow images: run tiles
+    // (config 26, 4x8 px x 32 ch tiles without overhang on 12x40, measured 67 vs 69 TFLOP/s for config 21: not picked)
+    // 8x16 (config 20) or 4x16 (config 21) pixel tiles.  Round 2 chose by M alone (>= 16000: 20).  Measured per shape in
+    // round 3 (tools/bench_conv.py incl. BENCH_DGRAD=1, B = 1 / 5 / 10): what decides is (a) how much of the tile grid is
+    // real pixels -- the padded dgrad domains are 14x42, 26x82, 50x162: 4-row tiles cover 50x162 with 88 % against 82 %
+    // (+8.6 %) -- and (b) whether the 8x16 grid has enough workgroups for 1280 slots: 600 of them lose 9-12 % to 1200
+    // 4x16 ones (128 -> 128 @24x80 at B = 5, 64 -> 32 @48x160, 128 -> 64 @24x80 at 2B), while on the small 14x42 domains at
+    // B >= 5 the larger tile wins by 7-11 % at equal coverage.
+    const int px = d->out_h * d->out_w, M = d->batch * px;
+    if (d->ch_out >= 32) {
+        const double cov20 = (double)px / ((double)cdiv(d->out_h, 8) * 8 * cdiv(d->out_w, 16) * 16);
+        const double cov21 = (double)px / ((double)cdiv(d->out_h, 4) * 4 * cdiv(d->out_w, 16) * 16);
+        const long long nblk20 = (long long)d->batch * cdiv(d->out_h, 8) * cdiv(d->out_w, 16) * cdiv(d->ch_out, 16);
+        if (cov21 > 1.04 * cov20) return 21;
+        if (M >= 4000) return nblk20 < 1000 ? 21 : 20;
+        return nblk20 >= 400 ? 20 : 21;
     }
-    if (d->ksize == 3 && d->stride == 2 && d->out_h == (d->in_h + 2 * d->pad - 3) / 2 + 1 && d->out_w == (d->in_w + 2 * d->pad - 3) / 2 + 1)
-        return 23;
+    return M >= 16000 ? 20 : 21;                           // 20/21/22 = 12/17/18 with conflict-free LDS rows (24x80 at 2B: 91.5 vs 88.4)
+}
+
+// Everything else (the 1x1 convs, 3x3 with an odd geometry): the implicit-GEMM tilings of this file.  Always answers.
+static int pick_igemm(const clslam_conv_desc* d) {
+    const bool bk32 = bk32_ok(d);
     if (d->ch_out % 32 != 0) return bk32 ? 6 : 4;
     if (!bk32) return 5;
     if (d->ch_out == 32) return 3;
     // measured on MI355X (tools/bench_conv.py): the 32x32 / 16x16x4 tiling wins or ties everywhere
     // except the widest-M 64-channel layers, where 64x32 is ~5 % ahead
-    if (d->ch_out == 64 && M >= 30000) return 3;
+    if (d->ch_out == 64 && d->batch * d->out_h * d->out_w >= 30000) return 3;
     return 2;
+}
+
+extern "C" int clslam_conv2d_pick_config(const clslam_conv_desc* d) {
+    if (const int cfg = pick_winograd(d)) return cfg;
+    if (const int cfg = pick_stream_k(d)) return cfg;
+    if (const int cfg = pick_patch(d)) return cfg;
+    return pick_igemm(d);
+}
+
+// An automatically picked persistent kernel (Winograd, stream-K) that does not fit its launch -- run tiles on a wide image,
+// scratch smaller than 64 KiB + one slab per workgroup -- is served by the tiled kernels: the pick with the persistent ones barred.
+static int tiled_config(const clslam_conv_desc* d) {
+    clslam_conv_desc tiled = *d;
+    tiled.config = -2;
+    return clslam_conv2d_pick_config(&tiled);
 }
 
 extern "C" int clslam_conv2d(const clslam_conv_desc* d, void* stream_) {
@@ -409,45 +366,27 @@ extern "C" int clslam_conv2d(const clslam_conv_desc* d, void* stream_) {
     CLSLAM_REQUIRE(!d->upsample_a || (d->in_h % 2 == 0 && d->in_w % 2 == 0), "conv2d: upsample needs even dims");
     CLSLAM_REQUIRE(d->pad_mode == CLSLAM_PAD_ZERO || (d->pad < d->in_h && d->pad < d->in_w), "conv2d: reflect pad too large");
     CLSLAM_REQUIRE(d->ch_b == 0 || d->src_b, "conv2d: src_b missing");
-    CLSLAM_REQUIRE(d->stride >= 1 && d->out_h == (d->in_h + 2 * d->pad - d->ksize) / d->stride + 1 &&
-                       d->out_w == (d->in_w + 2 * d->pad - d->ksize) / d->stride + 1,
-                   "conv2d: output size %dx%d does not match input %dx%d, ksize %d, stride %d, pad %d", d->out_h, d->out_w, d->in_h,
-                   d->in_w, d->ksize, d->stride, d->pad);
-    ConvK k;
-    k.src_a = d->src_a; k.src_b = d->src_b; k.wgt = d->weight; k.scale = d->scale; k.shift = d->shift;
-    k.residual = d->residual; k.out = d->out; k.actgrad_src = d->actgrad_src; k.actgrad_kind = d->actgrad_kind;
-    k.B = d->batch; k.Hi = d->in_h; k.Wi = d->in_w; k.Ca = d->ch_a; k.Cb = d->ch_b;
-    k.Ho = d->out_h; k.Wo = d->out_w; k.Cout = d->ch_out;
-    k.ksize = d->ksize; k.stride = d->stride; k.pad = d->pad; k.pad_mode = d->pad_mode;
-    k.ups = d->upsample_a; k.act = d->act;
-    k.M = d->batch * d->out_h * d->out_w;
-    k.tilesM = k.tilesN = k.nblk = 0;
-    if (k.M == 0) return CLSLAM_OK;
+    CLSLAM_REQUIRE(conv_size_consistent(d), "conv2d: output size %dx%d does not match input %dx%d, ksize %d, stride %d, pad %d",
+                   d->out_h, d->out_w, d->in_h, d->in_w, d->ksize, d->stride, d->pad);
     int cfg = d->config;
-    const bool bk32 = (Cin % 32 == 0) && (d->ch_b == 0 || d->ch_a % 32 == 0);
     if (cfg < 0) cfg = clslam_conv2d_pick_config(d);
     if (cfg == 40) {
         const int rc = conv3x3_wino_dispatch(d, stream);
         if (rc == CLSLAM_OK || d->config >= 0) return rc;
-        // an automatically picked Winograd launch that does not fit (scratch smaller than 64 KiB + one slab per workgroup): the
-        // direct kernels serve it, like an automatically picked stream-K configuration below
-        clslam_conv_desc tiled = *d;
-        tiled.config = -2;
-        cfg = clslam_conv2d_pick_config(&tiled);
+        cfg = tiled_config(d);
     }
     if (cfg >= 30) {
         const int rc = conv3x3_sk_dispatch(d, cfg, stream);
         if (rc == CLSLAM_OK || d->config >= 0) return rc;
-        // an automatically picked stream-K configuration that does not fit this geometry (run tiles on a wide
-        // image, scratch too small): the tiled kernel serves it
-        clslam_conv_desc tiled = *d;
-        tiled.config = -2;
-        cfg = clslam_conv2d_pick_config(&tiled);
+        cfg = tiled_config(d);
     }
     if (cfg >= 10) return conv3x3_patch_dispatch(d, cfg, stream);
     const bool need32 = (cfg <= 3 || cfg == 6);
-    if (need32 && !bk32) { set_error("conv2d: config %d needs channel multiples of 32", cfg); return CLSLAM_ERR_INVALID; }
+    if (need32 && !bk32_ok(d)) { set_error("conv2d: config %d needs channel multiples of 32", cfg); return CLSLAM_ERR_INVALID; }
     if ((cfg == 0 || cfg == 1) && d->ch_out % 32 != 0) { set_error("conv2d: config %d needs Cout %% 32 == 0", cfg); return CLSLAM_ERR_INVALID; }
+    ConvK k{conv_operands(d)};
+    k.ksize = d->ksize; k.stride = d->stride;
+    k.M = d->batch * d->out_h * d->out_w;
     switch (cfg) {
         case 0: return launch_conv<128, 64, 32, 32, 2>(k, stream);
         case 1: return launch_conv<64, 64, 32, 32, 2>(k, stream);

@@ -11,28 +11,15 @@
 // 8x16x64 configuration.  The next chunk is prefetched global->registers while the MFMAs of the current
 // chunk run; rows are padded to BK+4 floats so the ds_read_b128 fragment reads of neighbouring pixels
 // fall on distinct 16-byte bank slots.  Same operand convention as conv_fwd.hip (lane's float4 = four
-// consecutive k-steps), same fused epilogue.  Used for every stride-1 3x3 conv whose image is large
+// consecutive k-steps), same fused epilogue (fused_epilogue, conv_common.h).  Used for every stride-1 3x3 conv whose image is large
 // enough to tile (forward, and dgrad on the padded domain with pad = 2).
-#include "common.h"
-
-#include <type_traits>
+#include "conv_common.h"
 
 namespace clslam {
 
 constexpr int kSplitKMaxTiles = 16384;   // counters at the head of the caller's workspace (64 KiB)
 
-struct PatchK {
-    const float* __restrict__ src_a;
-    const float* __restrict__ src_b;
-    const float* __restrict__ wgt;
-    const float* __restrict__ scale;
-    const float* __restrict__ shift;
-    const float* __restrict__ residual;
-    const float* __restrict__ actgrad_src;
-    float* __restrict__ out;
-    int actgrad_kind;
-    int B, Hi, Wi, Ca, Cb, Ho, Wo, Cout;
-    int pad, pad_mode, ups, act;
+struct PatchK : ConvOperands {
     int tilesX, tilesY, tilesN, nblk;
     int n_fastest;   // block order inside an XCD: 1 = the output-channel tiles of one spatial tile are adjacent
     // split-K (small-M layers: too few tiles to fill 256 CUs).  ksplit blocks share an output tile, each
@@ -44,6 +31,7 @@ struct PatchK {
     unsigned* counters;   // [tiles], zero on entry, reset by the finishing block
     size_t ws_bytes;      // host side only
 };
+CLSLAM_FOLLOWS_CONV_OPERANDS(PatchK, tilesX)
 
 // RUN = true ("run tiles", for narrow images such as the 6x20 / 12x40 layers where a 4x16 rectangle
 // wastes half its lanes): the tile is a run of BM consecutive row-major output pixels of one image and
@@ -218,7 +206,7 @@ __global__ __launch_bounds__(256) void conv3x3_patch_kernel(PatchK p) {
     if constexpr (PRE_RES) {
 #pragma unroll
         for (int r = 0; r < NACC; ++r) {
-            const int m = wm0 + 4 * (lane >> 4) + r;
+            const int m = wm0 + acc_row<MF>(lane, r);
             int oy, ox;
             bool ok = true;
             if constexpr (RUN) {
@@ -276,10 +264,7 @@ __global__ __launch_bounds__(256) void conv3x3_patch_kernel(PatchK p) {
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int r = 0; r < NACC; ++r) {
-                    int row;
-                    if constexpr (MF == 32) row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    else row = 4 * (lane >> 4) + r;
-                    coherent_store(&slab[(wm0 + i * MF + row) * BN + wn0 + j * MF + (lane % MF)],
+                    coherent_store(&slab[(wm0 + i * MF + acc_row<MF>(lane, r)) * BN + wn0 + j * MF + (lane % MF)],
                                    NCH == 2 ? acc[i][j][0][r] + acc[i][j][NCH - 1][r] : acc[i][j][0][r]);
                 }
         stores_complete();      // every lane's slab stores are acknowledged ...
@@ -295,10 +280,7 @@ __global__ __launch_bounds__(256) void conv3x3_patch_kernel(PatchK p) {
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int r = 0; r < NACC; ++r) {
-                    int row;
-                    if constexpr (MF == 32) row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    else row = 4 * (lane >> 4) + r;
-                    const int e = (wm0 + i * MF + row) * BN + wn0 + j * MF + (lane % MF);
+                    const int e = (wm0 + i * MF + acc_row<MF>(lane, r)) * BN + wn0 + j * MF + (lane % MF);
                     float sum = 0.f;
                     for (int sp = 0; sp < p.ksplit; ++sp) sum += coherent_load(&gather[(size_t)sp * tiles_total * (BM * BN) + e]);
                     acc[i][j][0][r] = sum;
@@ -306,18 +288,9 @@ __global__ __launch_bounds__(256) void conv3x3_patch_kernel(PatchK p) {
                 }
     }
 
-    // ---- epilogue --------------------------------------------------------------------------------
-    // Three straight-line phases: (1) the optional operands (residual, activation-gradient source) of ALL the lane's elements
-    // loaded back to back from clamped (always valid) addresses, (2) every value computed with the activation switch OUTSIDE the
-    // element loop, (3) all stores back to back.  The element-by-element form (load? - value - load? - store per element, the
-    // activation's branches in between) made hipcc put an `s_waitcnt vmcnt(0)` in front of every load and store: eight serial
-    // memory round trips per workgroup, ~5 us of its ~11 us life on the 16-channel layers (round 5).
-    constexpr int NE = TM * TN * NACC;
+    // ---- epilogue: BN/bias, residual, activation, NHWC store (lanes run along channels) ------------------
     auto element = [&](int i, int j, int r, bool& ok) -> size_t {
-        int row;
-        if constexpr (MF == 32) row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        else row = 4 * (lane >> 4) + r;
-        const int m = wm0 + i * MF + row;
+        const int m = wm0 + i * MF + acc_row<MF>(lane, r);
         const int n = n0 + wn0 + j * MF + (lane % MF);
         int oy, ox;
         if constexpr (RUN) {
@@ -331,70 +304,9 @@ __global__ __launch_bounds__(256) void conv3x3_patch_kernel(PatchK p) {
         }
         return (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + min(n, p.Cout - 1);
     };
-    float vals[TM][TN][NACC], resq[TM][TN][NACC], agq[TM][TN][NACC];
-    const bool has_res = !PRE_RES && p.residual != nullptr, has_ag = p.actgrad_src != nullptr;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < NACC; ++r) {
-                if constexpr (PRE_RES) resq[i][j][r] = resv[r];
-                else resq[i][j][r] = 0.f;
-                agq[i][j][r] = 1.f;
-            }
-    if (has_res) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NACC; ++r) { bool ok; resq[i][j][r] = p.residual[element(i, j, r, ok)]; }
-    }
-    if (has_ag) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NACC; ++r) { bool ok; agq[i][j][r] = p.actgrad_src[element(i, j, r, ok)]; }
-    }
-    auto values = [&](auto act_tag) {
-        constexpr int ACT = decltype(act_tag)::value;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NACC; ++r) {
-                    float v = (NCH == 2 ? acc[i][j][0][r] + acc[i][j][NCH - 1][r] : acc[i][j][0][r]) * scv[j] + shv[j];
-                    v += resq[i][j][r];
-                    vals[i][j][r] = ACT < 0 ? apply_act(v, p.act) : apply_act(v, ACT);
-                }
-    };
-    if (p.act == CLSLAM_ACT_ELU) values(std::integral_constant<int, CLSLAM_ACT_ELU>{});
-    else if (p.act == CLSLAM_ACT_RELU) values(std::integral_constant<int, CLSLAM_ACT_RELU>{});
-    else if (p.act == CLSLAM_ACT_NONE) values(std::integral_constant<int, CLSLAM_ACT_NONE>{});
-    else values(std::integral_constant<int, -1>{});
-    if (has_ag) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NACC; ++r) vals[i][j][r] *= act_grad_from_output(agq[i][j][r], p.actgrad_kind);
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < NACC; ++r) {
-                bool ok;
-                const size_t o = element(i, j, r, ok);
-                if (ok) p.out[o] = vals[i][j][r];
-            }
-    (void)NE;
+    fused_epilogue<TM, TN, NACC, PRE_RES, CLSLAM_ACT_ELU, CLSLAM_ACT_RELU, CLSLAM_ACT_NONE>(
+        p, scv, shv, resv,
+        [&](int i, int j, int r) { return NCH == 2 ? acc[i][j][0][r] + acc[i][j][NCH - 1][r] : acc[i][j][0][r]; }, element);
 }
 
 // SKOK: the configuration has a split-K instantiation (the small-M ones: 20-23)
@@ -420,14 +332,13 @@ static int launch_patch(PatchK k, hipStream_t stream) {
     k.ksplit = ksplit;
     k.nblk = tiles * ksplit;
     k.n_fastest = ((size_t)k.Cout * 9 * (k.Ca + k.Cb) * 4 <= (size_t)(2 << 20)) ? 1 : 0;
-    if (const char* e = getenv("CLSLAM_N_FASTEST")) k.n_fastest = atoi(e);
     if constexpr (SKOK) {
         if (ksplit > 1) {
-            conv_launch(conv3x3_patch_kernel<TH, TW, BN, BK, MF, WGM, RUN, LDPAD, S, true>, k.nblk, stream, k);
+            conv_launch(conv3x3_patch_kernel<TH, TW, BN, BK, MF, WGM, RUN, LDPAD, S, true>, k.nblk, 256, stream, k);
             return check_launch("conv3x3_patch(split-K)");
         }
     }
-    conv_launch(conv3x3_patch_kernel<TH, TW, BN, BK, MF, WGM, RUN, LDPAD, S, false>, k.nblk, stream, k);
+    conv_launch(conv3x3_patch_kernel<TH, TW, BN, BK, MF, WGM, RUN, LDPAD, S, false>, k.nblk, 256, stream, k);
     return check_launch("conv3x3_patch");
 }
 
@@ -439,17 +350,12 @@ int conv3x3_patch_dispatch(const clslam_conv_desc* d, int cfg, hipStream_t strea
         set_error("conv2d: patch configs need a 3x3 conv with stride 1 (configs 10-22) or 2 (config 23)");
         return CLSLAM_ERR_INVALID;
     }
-    if (d->out_h != (d->in_h + 2 * d->pad - 3) / st + 1 || d->out_w != (d->in_w + 2 * d->pad - 3) / st + 1) {
+    if (!same_size_3x3(d, st)) {
         set_error("conv2d: inconsistent output size for the patch kernel");
         return CLSLAM_ERR_INVALID;
     }
-    PatchK k;
-    k.src_a = d->src_a; k.src_b = d->src_b; k.wgt = d->weight; k.scale = d->scale; k.shift = d->shift;
-    k.residual = d->residual; k.actgrad_src = d->actgrad_src; k.out = d->out; k.actgrad_kind = d->actgrad_kind;
-    k.B = d->batch; k.Hi = d->in_h; k.Wi = d->in_w; k.Ca = d->ch_a; k.Cb = d->ch_b; k.Ho = d->out_h; k.Wo = d->out_w;
-    k.Cout = d->ch_out; k.pad = d->pad; k.pad_mode = d->pad_mode; k.ups = d->upsample_a; k.act = d->act;
-    k.tilesX = k.tilesY = k.tilesN = k.nblk = 0; k.n_fastest = 0;
-    k.ksplit = 1; k.ws = nullptr; k.counters = nullptr; k.ws_bytes = 0;
+    PatchK k{conv_operands(d)};
+    k.ksplit = 1;
     if (d->workspace && d->workspace_bytes > (size_t)kSplitKMaxTiles * sizeof(unsigned)) {
         k.counters = (unsigned*)d->workspace;
         k.ws = (float*)((char*)d->workspace + (size_t)kSplitKMaxTiles * sizeof(unsigned));

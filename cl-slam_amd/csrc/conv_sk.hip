@@ -21,8 +21,10 @@
 //     ds_read_b128 fragment reads (16 consecutive rows x 4 slots) are bank-conflict free without padding.
 //     Zero padding, reflection, nearest-2x upsampling and the skip concat are per-lane address arithmetic of the
 //     DMA (out-of-image lanes fetch from a zero page).
-// Same fused epilogue and operand convention as conv_patch.hip (lane's float4 = four consecutive k-steps).
-#include "common.h"
+// Same operand block (ConvOperands, conv_common.h) and operand convention as conv_patch.hip (lane's float4 = four consecutive
+// k-steps).  The epilogue computes what fused_epilogue (conv_common.h) computes, in a form of its own on purpose: a lane holds
+// four consecutive channels of one pixel here, so operands and results move as float4.
+#include "conv_common.h"
 
 #include <mutex>
 #include <unordered_map>
@@ -36,18 +38,7 @@ constexpr int kSkMaxGroups = 4096;
 constexpr int kSkSlabOffsetBytes = 64 << 10;
 constexpr unsigned kSkSpinLimit = 1u << 22;
 
-struct SkK {
-    const float* __restrict__ src_a;
-    const float* __restrict__ src_b;
-    const float* __restrict__ wgt;
-    const float* __restrict__ scale;
-    const float* __restrict__ shift;
-    const float* __restrict__ residual;
-    const float* __restrict__ actgrad_src;
-    float* __restrict__ out;
-    int actgrad_kind;
-    int B, Hi, Wi, Ca, Cb, Ho, Wo, Cout;
-    int pad, pad_mode, ups, act;
+struct SkK : ConvOperands {
     int tilesX, tilesY, tilesN, tiles, NC, G;
     long long units;
     float* slabs;        // [G][BM*BN] raw partial tiles
@@ -56,6 +47,7 @@ struct SkK {
     unsigned epoch;      // value a producer publishes in this launch (non-zero, different for consecutive eager launches)
     int dbg;             // measurement probes (CLSLAM_SK_DBG): 1 no epilogue, 2 no hand-off, 4 no MFMA, 8 no DMA
 };
+CLSLAM_FOLLOWS_CONV_OPERANDS(SkK, tilesX)
 
 // patch rows (pixels) reserved per LDS stage for run tiles; stride-2 runs (the 6x20 outputs of the last stage entry: one
 // 128-pixel run covers a whole 120-pixel image, 13 x 41 input pixels) need the larger band
@@ -489,15 +481,7 @@ static int launch_sk(SkK k, const clslam_conv_desc* d, hipStream_t stream) {
     k.flags = (unsigned*)d->workspace + kSkFlagOffset;
     k.epoch = sk_next_epoch(d->workspace);
     k.slabs = (float*)((char*)d->workspace + kSkSlabOffsetBytes);
-    auto kern = conv3x3_sk_kernel<TH, TW, RUN, S, BN, NWM, NWN>;
-#if CLSLAM_DEVICE_BUILD
-    hipEvent_t e0, e1;
-    if (profile_next_events(&e0, &e1)) {
-        hipExtLaunchKernelGGL(kern, dim3(G), dim3(NWM * NWN * 64), 0, stream, e0, e1, 0, k);
-        return check_launch("conv3x3_sk");
-    }
-#endif
-    hipLaunchKernelGGL(kern, dim3(G), dim3(NWM * NWN * 64), 0, stream, k);
+    conv_launch(conv3x3_sk_kernel<TH, TW, RUN, S, BN, NWM, NWN>, G, NWM * NWN * 64, stream, k);
     return check_launch("conv3x3_sk");
 }
 
@@ -505,14 +489,8 @@ static int launch_sk(SkK k, const clslam_conv_desc* d, hipStream_t stream) {
 int conv3x3_sk_dispatch(const clslam_conv_desc* d, int cfg, hipStream_t stream) {
     const int st = d->stride;
     if (d->ksize != 3 || (st != 1 && st != 2)) { set_error("conv2d: stream-K configs need a 3x3 conv with stride 1 or 2"); return CLSLAM_ERR_INVALID; }
-    SkK k;
-    k.src_a = d->src_a; k.src_b = d->src_b; k.wgt = d->weight; k.scale = d->scale; k.shift = d->shift;
-    k.residual = d->residual; k.actgrad_src = d->actgrad_src; k.out = d->out; k.actgrad_kind = d->actgrad_kind;
-    k.B = d->batch; k.Hi = d->in_h; k.Wi = d->in_w; k.Ca = d->ch_a; k.Cb = d->ch_b; k.Ho = d->out_h; k.Wo = d->out_w;
-    k.Cout = d->ch_out; k.pad = d->pad; k.pad_mode = d->pad_mode; k.ups = d->upsample_a; k.act = d->act;
-    k.tilesX = k.tilesY = k.tilesN = k.tiles = k.NC = k.G = 0; k.units = 0; k.slabs = nullptr; k.flags = nullptr;
-    k.epoch = 1u; k.b_fastest = 0;
-    k.dbg = 0;
+    SkK k{conv_operands(d)};
+    k.epoch = 1u;
     if (const char* e = getenv("CLSLAM_SK_DBG")) k.dbg = atoi(e);
     const bool s2 = st == 2;
     switch (cfg) {

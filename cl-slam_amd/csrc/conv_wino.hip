@@ -22,7 +22,8 @@
 //   * work = (region, stage) units cut into G equal ranges exactly like conv_sk.hip (same flags, epochs, fixed-order gather).
 //     A region is RB images x RH x RW tiles (<= 64), chosen per layer by the host for coverage: 8x8 tiles on 48x160, 6x10 on
 //     24x80 and 12x40, two whole 6x20 images.
-// Same operand conventions and fused epilogue as the other convolution kernels (scale/shift, residual, activation).
+// Same operand conventions as the other convolution kernels, and the arithmetic of their fused epilogue (fused_epilogue,
+// conv_common.h: scale/shift, residual, activation) in a float4-per-lane form of its own, deliberately separate.
 //
 // Two waves per SIMD, and why (round 5, tools/micro/, profiles/r05_wino_*): the first version kept all 16 positions of 32 tiles x
 // 32 channels in ONE 512-register wave per SIMD (v_mfma_f32_32x32x2_f32, accumulators pinned in a0-a255 by name because sixteen
@@ -34,8 +35,7 @@
 // time: 6200-7800 cycles per stage for 4096 cycles of MFMAs, 56-103 TFLOP/s.  With the accumulators split over eight waves one
 // wave's transform / LDS reads / DMA issue run while its partner on the SIMD holds the matrix pipe: 60-111 TFLOP/s
 // (profiles/r05_wino_microbench.txt), and the kernel needs no inline-asm register file.
-#include "common.h"
-#include <type_traits>
+#include "conv_common.h"
 
 
 namespace clslam {
@@ -537,10 +537,9 @@ static void wino_pick_region(int B, int Ho, int Wo, int& RB, int& RH, int& RW) {
 }
 
 int conv3x3_wino_supported(const clslam_conv_desc* d) {
-    return d->weight_wino != nullptr && d->ksize == 3 && d->stride == 1 && d->ch_b == 0 && !d->upsample_a && d->pad_mode == CLSLAM_PAD_ZERO &&
+    return d->weight_wino != nullptr && same_size_3x3(d, 1) && d->ch_b == 0 && !d->upsample_a && d->pad_mode == CLSLAM_PAD_ZERO &&
            d->ch_a % 16 == 0 && d->ch_out % 16 == 0 && (d->pad == 1 || d->pad == 2) && d->actgrad_src == nullptr &&
-           (d->act == CLSLAM_ACT_NONE || d->act == CLSLAM_ACT_RELU) &&
-           d->out_h == d->in_h + 2 * d->pad - 2 && d->out_w == d->in_w + 2 * d->pad - 2;
+           (d->act == CLSLAM_ACT_NONE || d->act == CLSLAM_ACT_RELU);
 }
 
 // (tile, stage) units per persistent workgroup: what decides whether this kernel pays.  Its fixed costs per launch -- prologue, one
@@ -600,14 +599,7 @@ int conv3x3_wino_dispatch(const clslam_conv_desc* d, hipStream_t stream) {
     k.epoch = sk_next_epoch(d->workspace);
     k.slabs = (float*)((char*)d->workspace + kWinoSlabOffsetBytes);
     k.trace = (unsigned long long*)((char*)d->workspace + kWinoSlabOffsetBytes + (size_t)G * kWinoSlabFloats * sizeof(float));
-#if CLSLAM_DEVICE_BUILD
-    hipEvent_t e0, e1;
-    if (profile_next_events(&e0, &e1)) {
-        hipExtLaunchKernelGGL(conv3x3_wino8_kernel, dim3(G), dim3(512), 0, stream, e0, e1, 0, k);
-        return check_launch("conv3x3_wino");
-    }
-#endif
-    hipLaunchKernelGGL(conv3x3_wino8_kernel, dim3(G), dim3(512), 0, stream, k);
+    conv_launch(conv3x3_wino8_kernel, G, 512, stream, k);
     return check_launch("conv3x3_wino");
 }
 

@@ -110,13 +110,13 @@ One-line mutations of the kernel sources (CPU emulator, scratch copies) and the 
 tests/test_conv.py and tests/test_conv_bwd.py as they stood caught it on the emulator:
   conv_sk.hip    `min(base + q, ncon - 1)` -> `min(base + q, 3)`: a contributor slab past the fourth re-read as the fourth
                      test_forward_twin[denc.layer3.0.conv2-cfg33] (+ cfg 31 / 32 twins)              before: yes (33 with 16 groups)
-  conv_fwd.hip   picker: `units128 >= 1280 ? 32 : 33` -> `>= 640`
+  conv_fwd.hip   pick_stream_k: `units128 >= 1280 ? 32 : 33` -> `>= 640`
                      test_picker_coverage (a penc row is no longer what PICKS records)               before: no
-  conv_fwd.hip   picker: band_fits `<= 544` -> `<= 500` (the 13 x 41 band of the 6x20 stride-2 run no longer "fits")
+  conv_fwd.hip   pick_stream_k: band_fits `<= 544` -> `<= 500` (the 13 x 41 band of the 6x20 stride-2 run no longer "fits")
                      test_picker_coverage (a denc row is no longer what PICKS records)               before: no
   conv_fwd.hip   picker / dispatch: a new `case 7:` in the switch of clslam_conv2d
                      test_picker_coverage (neither picked nor in EXPLICIT_ONLY: [7])                 before: no
-  conv_fwd.hip   stream-K fallback: `if (rc == CLSLAM_OK || d->config >= 0) return rc;` -> `return rc;`
+  conv_fwd.hip   stream-K fallback of clslam_conv2d: `if (rc == CLSLAM_OK || d->config >= 0) return rc;` -> `return rc;`
                      test_fallbacks_of_conv2d[ddec.upconv_4_0-5-33]                                  before: no
   conv_fwd.hip   Winograd fallback: the same line of the Winograd block
                      test_fallbacks_of_conv2d[denc.layer4.1.conv1-5-40]                              before: yes
