@@ -8,6 +8,9 @@
 //   topk_sort_kernel : bitonic sort of 4096 (score, id) pairs per workgroup in LDS, first k kept; a second
 //                      pass over the per-chunk winners merges more than 4096 vectors
 // Order: descending score, equal scores by ascending position (deterministic; faiss's heap leaves ties unspecified).
+// A score that is NaN or not above -FLT_MAX (-inf, -FLT_MAX itself) is never a match: faiss's result heap starts at
+// (-FLT_MAX, -1) and admits only a greater score, so such a vector is not returned at all.  The places past the matches hold
+// (-FLT_MAX, -1); no real id ever follows a -1.  (-inf used to keep its id and sort BEHIND the padding: ids -1 then a real id.)
 #include "common.h"
 
 #include <cfloat>
@@ -59,9 +62,8 @@ __global__ __launch_bounds__(256) void topk_sort_kernel(const float* __restrict_
         if (g < n) {
             const int src = id ? id[g] : g;
             if (src >= 0) {
-                s = v[g];
-                if (!(s == s)) s = -FLT_MAX;             // NaN similarity: never a match
-                i = src;
+                const float sv = v[g];
+                if (sv > -FLT_MAX) { s = sv; i = src; }  // NaN or not above -FLT_MAX (-inf): never a match -> padding
             }
         }
         key[e] = s; idx[e] = i;

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 F64 = torch.float64
-ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_ELU, ACT_HSWISH, ACT_HSIGMOID = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
 
 
@@ -28,6 +28,10 @@ def _nchw(t, dtype):
 
 
 def act_fn(v, act):
+    if act == ACT_HSWISH:                       # common.h apply_act: v * clamp(v + 3, 0, 6) / 6
+        return v * torch.clamp(v + 3, 0, 6) / 6
+    if act == ACT_HSIGMOID:
+        return torch.clamp(v + 3, 0, 6) / 6
     return F.relu(v) if act == ACT_RELU else F.elu(v) if act == ACT_ELU else v
 
 
