@@ -278,8 +278,8 @@ extern "C" int clslam_dispconv_wgrad(const float* dz, const float* x, float* par
 
 extern "C" int clslam_pose_head_fwd(const float* x, const float* w2, const float* b2, float* mean, float* pose, int n,
                                     int hw, void* stream) {
+    if (!n) return CLSLAM_OK;      // an empty batch has no storage: nothing to check, nothing to launch
     CLSLAM_REQUIRE(x && w2 && b2 && mean && pose, "pose_head_fwd: null");
-    if (!n) return CLSLAM_OK;
     hipLaunchKernelGGL(pose_head_fwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, x, w2, b2, mean, pose, hw);
     return check_launch("pose_head_fwd");
 }
