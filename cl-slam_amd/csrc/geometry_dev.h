@@ -10,9 +10,16 @@ namespace clslam {
 struct Pyramid {
     const float* disp[4];
     int h[4], w[4];
-    int n;
-    int base;      // first scale of THIS launch (warp_fwd / loss_bwd2 / disp_grad take a sub-range of the pyramid: grid index + base)
+    int n;         // read by disp_grad_kernel only: 0 = its single-map form; the launches of one map elsewhere set 1, a pyramid 4
 };
+
+// the four scales of one launch: disp[s] (B, H >> s, W >> s)
+inline Pyramid make_pyramid(const float* const* disp, int H, int W) {
+    Pyramid pyr;
+    pyr.n = 4;
+    for (int k = 0; k < 4; ++k) { pyr.disp[k] = disp[k]; pyr.h[k] = H >> k; pyr.w[k] = W >> k; }
+    return pyr;
+}
 
 // EVERY function between a disparity and a bilinear cell below has floating-point contraction switched off.  The forward
 // (warp_fwd), the loss backward and the diagnostic read-out each re-derive the sampling position of a pixel, and the

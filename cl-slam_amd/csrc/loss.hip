@@ -86,14 +86,14 @@ __global__ __launch_bounds__(256) void photo_automask_kernel(const float* __rest
                                                              const float* __restrict__ idmap, const float* __restrict__ noise_all,
                                                              unsigned char* __restrict__ sel_all, float* __restrict__ coef_sel_all,
                                                              float* __restrict__ partial_all, int B, int H, int W, int tilesX,
-                                                             unsigned long long seed, unsigned long long rng_offset, int sc0) {
+                                                             unsigned long long seed, unsigned long long rng_offset) {
     // The two source frames of a pixel travel as ONE packed pair (f32x2 = v_pk_* arithmetic, ds_read_b64): the kernel is
     // VALU-bound (~900 issue slots per pixel before, two thirds of them per frame), not LDS- or HBM-bound.
     __shared__ float tl[3][PA_PH * PA_PW];   // target
     __shared__ f32x2 tw[3][PA_PH * PA_PW];   // warped (frame 0, frame 1)
     __shared__ float red[4];
     const float C1 = 0.0001f, C2 = 0.0009f;
-    const int b = blockIdx.y, sc = blockIdx.z + sc0;      // sc0: first scale of this launch
+    const int b = blockIdx.y, sc = blockIdx.z;
     const int HW = H * W;
     const int ty = blockIdx.x / tilesX, tx = blockIdx.x - ty * tilesX;
     const int y0 = ty * PA_TH, x0 = tx * PA_TW;
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void loss_bwd2_kernel(Pyramid pyr, const unsig
     __shared__ f32x2 cs[LB_PH * LB_PW][5];
     __shared__ unsigned char ss[LB_PH * LB_PW];
     __shared__ double red[4][24];     // the pose-gradient sums leave the thread in double (wave_sum_f64)
-    const int b = blockIdx.y, sc = blockIdx.z + pyr.base;
+    const int b = blockIdx.y, sc = blockIdx.z;
     const int HW = H * W;
     const int ty = blockIdx.x / tilesX, tx = blockIdx.x - ty * tilesX;
     const int y0 = ty * LB_TH, x0 = tx * LB_TW;
@@ -638,98 +638,6 @@ __global__ __launch_bounds__(256) void photo_grad_kernel(const unsigned char* __
     }
 }
 
-// Fused loss backward for the whole pyramid (one launch): photometric gradient -> grid_sample / projection
-// / depth backward.  grid (nblk, B, nscale).  Writes ddisp_up[s,b,y,x] and dP_partial[s][b][blk][24].
-__global__ __launch_bounds__(256) void loss_bwd_kernel(Pyramid pyr, const unsigned char* __restrict__ sel_all,
-                                                       const float* __restrict__ coef_all, const float* __restrict__ warped_all,
-                                                       const float* __restrict__ target, const float* __restrict__ src_m1,
-                                                       const float* __restrict__ src_p1, const float* __restrict__ Kinv,
-                                                       const float* __restrict__ P, const float* __restrict__ sample_w,
-                                                       float* __restrict__ ddisp_up_all, double* __restrict__ dP_partial, int B,
-                                                       int H, int W, float da, float db, int dmode, int pix_per_block) {
-    __shared__ double red[4][24];
-    const int b = blockIdx.y, sc = blockIdx.z;
-    const int HW = H * W;
-    const int h = pyr.h[sc], w = pyr.w[sc];
-    const float* disp_s = pyr.disp[sc];
-    const unsigned char* sl = sel_all + ((size_t)sc * B + b) * HW;
-    const float* coef = coef_all + (size_t)sc * 2 * B * 9 * HW;
-    const float* warped = warped_all + (size_t)sc * 2 * B * 3 * HW;
-    float* ddisp_up = ddisp_up_all + (size_t)sc * B * HW;
-    const float wq = sample_w[b] / ((float)H * (float)W) / 4.f;
-    const int p0 = blockIdx.x * pix_per_block, p1 = min(HW, p0 + pix_per_block);
-    double dPacc[24];
-#pragma unroll
-    for (int k = 0; k < 24; ++k) dPacc[k] = 0.0;
-    const float* Ki = Kinv + (size_t)b * 16;
-    for (int pi = p0 + (int)threadIdx.x; pi < p1; pi += 256) {
-        const int x = pi % W, y = pi / W;
-        const float disp = upsample_disp(disp_s + (size_t)b * h * w, h, w, H, W, y, x);
-        const float dep = disp_to_depth_dev(disp, da, db, dmode);
-        const float fx = (float)x, fy = (float)y;
-        float cam[3], X[3];
-        backproject_px(Ki, fx, fy, dep, cam, X);
-        float ddepth = 0.f;
-#pragma unroll 1
-        for (int fi = 0; fi < 2; ++fi) {   // not unrolled: halves the live registers (occupancy 2 -> 4 waves/SIMD)
-            const int n = fi * B + b;
-            float g3[3];
-            photo_grad_px(sl, coef + (size_t)n * 9 * HW, warped + (size_t)n * 3 * HW, target + (size_t)b * 3 * HW, H, W, y, x,
-                          (unsigned char)(2 + fi), g3);
-            const float* Pm = P + (size_t)n * 12;
-            float u, v, den;
-            project_px(Pm, X, u, v, den);
-            const Sample s = sample_coords(u, v, H, W);
-            const float wx1 = s.ix - (float)s.x0, wy1 = s.iy - (float)s.y0;
-            const float wx0 = (float)(s.x0 + 1) - s.ix, wy0 = (float)(s.y0 + 1) - s.iy;
-            const bool x1ok = s.x0 + 1 < W, y1ok = s.y0 + 1 < H;
-            const float* src = (fi == 0 ? src_m1 : src_p1) + (size_t)b * 3 * HW;
-            float gix = 0.f, giy = 0.f;
-            for (int c = 0; c < 3; ++c) {
-                const float g = g3[c] * wq;
-                const float* pl = src + (size_t)c * HW;
-                const float nw = pl[s.y0 * W + s.x0];
-                const float ne = x1ok ? pl[s.y0 * W + s.x0 + 1] : 0.f;
-                const float sw = y1ok ? pl[(s.y0 + 1) * W + s.x0] : 0.f;
-                const float se = (x1ok && y1ok) ? pl[(s.y0 + 1) * W + s.x0 + 1] : 0.f;
-                gix += g * (-nw * wy0 + ne * wy0 - sw * wy1 + se * wy1);
-                giy += g * (-nw * wx0 - ne * wx1 + sw * wx0 + se * wx1);
-            }
-            const float du = gix * s.mx, dv = giy * s.my;
-            float dp[3];
-            dp[0] = du / den;
-            dp[1] = dv / den;
-            dp[2] = -(du * u + dv * v) / den;
-            // dPacc is indexed with compile-time constants only (a runtime index would spill it to scratch)
-            if (fi == 0) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    dPacc[i * 4 + 0] += dp[i] * X[0]; dPacc[i * 4 + 1] += dp[i] * X[1];
-                    dPacc[i * 4 + 2] += dp[i] * X[2]; dPacc[i * 4 + 3] += dp[i];
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    dPacc[12 + i * 4 + 0] += dp[i] * X[0]; dPacc[12 + i * 4 + 1] += dp[i] * X[1];
-                    dPacc[12 + i * 4 + 2] += dp[i] * X[2]; dPacc[12 + i * 4 + 3] += dp[i];
-                }
-            }
-            ddepth += ddepth_from_duv(Pm, cam, du, dv, 1.f / den);
-        }
-        ddisp_up[(size_t)b * HW + pi] = (dmode == 2) ? -db * dep * dep * ddepth : -dep / disp * ddepth;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 24; ++k) {
-        const double s = wave_sum_f64(dPacc[k]);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 24)
-        dP_partial[(((size_t)sc * B + b) * gridDim.x + blockIdx.x) * 24 + threadIdx.x] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
 // ------------------------------------------------------------------------------------------------
 // dz[b,i,j] = sigmoid'(disp) * ( bilinear-upsample^T(ddisp_up)[b,i,j] + smoothness gradient )
 struct DzPtrs { float* dz[4]; };
@@ -796,7 +704,7 @@ __global__ __launch_bounds__(256) void disp_grad_kernel(const float* ddisp_up, c
 // read consecutive X), then xor-shuffle reduce: every scale exposes B*H*W threads of equal work.
 __global__ __launch_bounds__(256) void disp_grad_coop_kernel(const float* __restrict__ ddisp_up_all, const float* __restrict__ smooth_all,
                                                              int n_smooth, int B, int H, int W, Pyramid pyr, DzPtrs dzp) {
-    const int sc = blockIdx.y + pyr.base;
+    const int sc = blockIdx.y;
     const int h = pyr.h[sc], w = pyr.w[sc];
     const int f = H / h, G = f * f;
     const float* __restrict__ disp = pyr.disp[sc];
@@ -911,17 +819,10 @@ extern "C" int clslam_disp_mean(const float* disp, float* means, int batch, int 
     CLSLAM_REQUIRE(disp && means, "disp_mean: null");
     if (!batch) return CLSLAM_OK;
     Pyramid pyr;
-    pyr.n = 1; pyr.base = 0; pyr.disp[0] = disp; pyr.h[0] = 1; pyr.w[0] = hw;
+    pyr.n = 1; pyr.disp[0] = disp; pyr.h[0] = 1; pyr.w[0] = hw;
     for (int k = 1; k < 4; ++k) { pyr.disp[k] = nullptr; pyr.h[k] = pyr.w[k] = 0; }
     hipLaunchKernelGGL(disp_mean_kernel, dim3(DM_CHUNKS, batch, 1), dim3(256), 0, (hipStream_t)stream, pyr, means, batch);
     return check_launch("disp_mean");
-}
-
-static Pyramid make_pyramid(const float* const* disp, int H, int W) {
-    Pyramid pyr;
-    pyr.n = 4; pyr.base = 0;
-    for (int k = 0; k < 4; ++k) { pyr.disp[k] = disp[k]; pyr.h[k] = H >> k; pyr.w[k] = W >> k; }
-    return pyr;
 }
 
 // psum (4,B,chunks) for the four disparity maps disp[s] (B,H>>s,W>>s), one launch
@@ -937,43 +838,31 @@ extern "C" int clslam_disp_mean_pyramid(const float* const* disp, float* psum, i
 // sel (4,B,H,W), coef_sel (4,B,9,H,W)|NULL (training only), partial (4,B,clslam_automask_blocks).
 static int photo_automask_launch(const float* warped, const float* target, const float* idmap, const float* noise,
                                  unsigned char* sel, float* coef_sel, float* partial, int batch, int H, int W,
-                                 unsigned long long seed, unsigned long long offset, int scale_lo, int scale_count, void* stream) {
+                                 unsigned long long seed, unsigned long long offset, void* stream) {
     CLSLAM_REQUIRE(warped && target && idmap && sel && partial && H >= 2 && W >= 2, "photo_automask_pyramid: bad args");
-    CLSLAM_REQUIRE(scale_lo >= 0 && scale_count >= 0 && scale_lo + scale_count <= 4, "photo_automask_pyramid: scales [%d, %d) outside the pyramid",
-                   scale_lo, scale_lo + scale_count);
-    if (!batch || !scale_count) return CLSLAM_OK;
+    if (!batch) return CLSLAM_OK;
     const int nblk = clslam_automask_blocks(H, W);   // = number of 8 x 64 tiles
     const int tilesX = cdiv(W, PA_TW);
     if (coef_sel)
-        hipLaunchKernelGGL(photo_automask_kernel<true>, dim3(nblk, batch, scale_count), dim3(256), 0, (hipStream_t)stream, warped, target,
-                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset, scale_lo);
+        hipLaunchKernelGGL(photo_automask_kernel<true>, dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, warped, target,
+                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset);
     else
-        hipLaunchKernelGGL(photo_automask_kernel<false>, dim3(nblk, batch, scale_count), dim3(256), 0, (hipStream_t)stream, warped, target,
-                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset, scale_lo);
+        hipLaunchKernelGGL(photo_automask_kernel<false>, dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, warped, target,
+                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset);
     return check_launch("photo_automask_pyramid");
 }
 
 extern "C" int clslam_photo_automask_pyramid(const float* warped, const float* target, const float* idmap, const float* noise,
                                              unsigned char* sel, float* coef_sel, float* partial, int batch, int H, int W,
                                              void* stream) {
-    return photo_automask_launch(warped, target, idmap, noise, sel, coef_sel, partial, batch, H, W, 0ull, 0ull, 0, 4, stream);
+    return photo_automask_launch(warped, target, idmap, noise, sel, coef_sel, partial, batch, H, W, 0ull, 0ull, stream);
 }
 
 extern "C" int clslam_photo_automask_pyramid_rng(const float* warped, const float* target, const float* idmap,
                                                  unsigned long long seed, unsigned long long offset, unsigned char* sel,
                                                  float* coef_sel, float* partial, int batch, int H, int W, void* stream) {
     CLSLAM_REQUIRE(seed != 0, "photo_automask_pyramid_rng: seed must be non-zero");
-    return photo_automask_launch(warped, target, idmap, nullptr, sel, coef_sel, partial, batch, H, W, seed, offset, 0, 4, stream);
-}
-
-// scales [scale_lo, scale_lo + scale_count) only: noise injected (noise != NULL), drawn in the kernel (seed != 0) or absent
-extern "C" int clslam_photo_automask_pyramid_range(const float* warped, const float* target, const float* idmap, const float* noise,
-                                                   unsigned long long seed, unsigned long long offset, unsigned char* sel,
-                                                   float* coef_sel, float* partial, int batch, int H, int W, int scale_lo,
-                                                   int scale_count, void* stream) {
-    CLSLAM_REQUIRE(!(noise && seed), "photo_automask_pyramid_range: injected noise and an in-kernel draw exclude each other");
-    return photo_automask_launch(warped, target, idmap, noise, sel, coef_sel, partial, batch, H, W, seed, offset, scale_lo, scale_count,
-                                 stream);
+    return photo_automask_launch(warped, target, idmap, nullptr, sel, coef_sel, partial, batch, H, W, seed, offset, stream);
 }
 
 extern "C" int clslam_tie_break_noise(float* out, size_t npix, unsigned long long seed, unsigned long long offset, void* stream) {
@@ -988,53 +877,20 @@ extern "C" int clslam_loss_bwd2_blocks(int H, int W) { return cdiv(H, LB_TH) * c
 
 // LDS-tiled fused loss backward on the selected-frame coefficients (clslam_photo_automask_pyramid);
 // dp_partial [4][B][clslam_loss_bwd2_blocks][24].
-extern "C" int clslam_loss_bwd2_pyramid_range(const float* const* disp, const unsigned char* sel, const float* coef_sel,
-                                              const float* warped, const float* target, const float* src_m1, const float* src_p1,
-                                              const float* inv_k, const float* proj, const float* sample_w, float* ddisp_up,
-                                              double* dp_partial, int batch, int H, int W, float min_depth, float max_depth,
-                                              int scale_lo, int scale_count, void* stream) {
-    CLSLAM_REQUIRE(disp && sel && coef_sel && warped && target && src_m1 && src_p1 && inv_k && proj && sample_w && ddisp_up &&
-                   dp_partial, "loss_bwd2_pyramid: null");
-    CLSLAM_REQUIRE(scale_lo >= 0 && scale_count >= 0 && scale_lo + scale_count <= 4, "loss_bwd2_pyramid: scales [%d, %d) outside the pyramid",
-                   scale_lo, scale_lo + scale_count);
-    float a, b; int mode;
-    depth_mode(min_depth, max_depth, &a, &b, &mode);
-    if (!batch || !scale_count) return CLSLAM_OK;
-    const int tilesX = cdiv(W, LB_TW);
-    Pyramid pyr = make_pyramid(disp, H, W);
-    pyr.base = scale_lo;
-    hipLaunchKernelGGL(loss_bwd2_kernel, dim3(clslam_loss_bwd2_blocks(H, W), batch, scale_count), dim3(256), 0, (hipStream_t)stream,
-                       pyr, sel, coef_sel, warped, target, src_m1, src_p1, inv_k, proj, sample_w, ddisp_up,
-                       dp_partial, batch, H, W, a, b, mode, tilesX);
-    return check_launch("loss_bwd2_pyramid");
-}
-
 extern "C" int clslam_loss_bwd2_pyramid(const float* const* disp, const unsigned char* sel, const float* coef_sel,
                                         const float* warped, const float* target, const float* src_m1, const float* src_p1,
                                         const float* inv_k, const float* proj, const float* sample_w, float* ddisp_up,
                                         double* dp_partial, int batch, int H, int W, float min_depth, float max_depth, void* stream) {
-    return clslam_loss_bwd2_pyramid_range(disp, sel, coef_sel, warped, target, src_m1, src_p1, inv_k, proj, sample_w, ddisp_up, dp_partial,
-                                          batch, H, W, min_depth, max_depth, 0, 4, stream);
-}
-
-extern "C" int clslam_loss_bwd_blocks(int H, int W) { return std::max(1, std::min(256, cdiv(H * W, 1024))); }
-
-// Fused photometric + view-synthesis backward of all four scales (one launch).  sel (4,B,H,W),
-// coef (4,2,B,9,H,W), warped (4,2,B,3,H,W); ddisp_up (4,B,H,W); dp_partial [4][B][nblk][24].
-extern "C" int clslam_loss_bwd_pyramid(const float* const* disp, const unsigned char* sel, const float* coef, const float* warped,
-                                       const float* target, const float* src_m1, const float* src_p1, const float* inv_k,
-                                       const float* proj, const float* sample_w, float* ddisp_up, double* dp_partial, int batch,
-                                       int H, int W, float min_depth, float max_depth, void* stream) {
-    CLSLAM_REQUIRE(disp && sel && coef && warped && target && src_m1 && src_p1 && inv_k && proj && sample_w && ddisp_up &&
-                   dp_partial, "loss_bwd_pyramid: null");
+    CLSLAM_REQUIRE(disp && sel && coef_sel && warped && target && src_m1 && src_p1 && inv_k && proj && sample_w && ddisp_up &&
+                   dp_partial, "loss_bwd2_pyramid: null");
     float a, b; int mode;
     depth_mode(min_depth, max_depth, &a, &b, &mode);
     if (!batch) return CLSLAM_OK;
-    const int nblk = clslam_loss_bwd_blocks(H, W);
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, make_pyramid(disp, H, W), sel, coef,
-                       warped, target, src_m1, src_p1, inv_k, proj, sample_w, ddisp_up, dp_partial, batch, H, W, a, b, mode,
-                       cdiv(H * W, nblk));
-    return check_launch("loss_bwd_pyramid");
+    const int tilesX = cdiv(W, LB_TW);
+    hipLaunchKernelGGL(loss_bwd2_kernel, dim3(clslam_loss_bwd2_blocks(H, W), batch, 4), dim3(256), 0, (hipStream_t)stream,
+                       make_pyramid(disp, H, W), sel, coef_sel, warped, target, src_m1, src_p1, inv_k, proj, sample_w, ddisp_up,
+                       dp_partial, batch, H, W, a, b, mode, tilesX);
+    return check_launch("loss_bwd2_pyramid");
 }
 
 extern "C" int clslam_loss_finalize(const clslam_loss_desc* d, void* stream) {
@@ -1075,25 +931,16 @@ extern "C" int clslam_disp_grad(const float* ddisp_up, const float* disp, const 
 }
 
 // all four scales in one launch: ddisp_up (4,B,H,W), smooth_aux [4][2+2*n_smooth], dz[s] (B,H>>s,W>>s)
-extern "C" int clslam_disp_grad_pyramid_range(const float* ddisp_up, const float* const* disp, const float* smooth_aux, int n_smooth,
-                                              float* const* dz, int batch, int H, int W, int scale_lo, int scale_count, void* stream) {
-    CLSLAM_REQUIRE(ddisp_up && disp && dz, "disp_grad_pyramid: null");
-    CLSLAM_REQUIRE(n_smooth == 0 || (smooth_aux && n_smooth < (W >> 3) - 1 && (H >> 3) >= 2), "disp_grad_pyramid: smoothness layout unsupported");
-    CLSLAM_REQUIRE(scale_lo >= 0 && scale_count >= 0 && scale_lo + scale_count <= 4, "disp_grad_pyramid: scales [%d, %d) outside the pyramid",
-                   scale_lo, scale_lo + scale_count);
-    if (!batch || !scale_count) return CLSLAM_OK;
-    DzPtrs dzp; for (int k = 0; k < 4; ++k) dzp.dz[k] = dz[k];
-    CLSLAM_REQUIRE(H % 8 == 0 && W % 8 == 0 && (size_t)batch * H * W < ((size_t)1 << 31), "disp_grad_pyramid: H, W must be multiples of 8");
-    Pyramid pyr = make_pyramid(disp, H, W);
-    pyr.base = scale_lo;
-    hipLaunchKernelGGL(disp_grad_coop_kernel, dim3(cdiv(batch * H * W, 256), scale_count), dim3(256), 0, (hipStream_t)stream, ddisp_up,
-                       smooth_aux, n_smooth, batch, H, W, pyr, dzp);
-    return check_launch("disp_grad_pyramid");
-}
-
 extern "C" int clslam_disp_grad_pyramid(const float* ddisp_up, const float* const* disp, const float* smooth_aux, int n_smooth,
                                         float* const* dz, int batch, int H, int W, void* stream) {
-    return clslam_disp_grad_pyramid_range(ddisp_up, disp, smooth_aux, n_smooth, dz, batch, H, W, 0, 4, stream);
+    CLSLAM_REQUIRE(ddisp_up && disp && dz, "disp_grad_pyramid: null");
+    CLSLAM_REQUIRE(n_smooth == 0 || (smooth_aux && n_smooth < (W >> 3) - 1 && (H >> 3) >= 2), "disp_grad_pyramid: smoothness layout unsupported");
+    if (!batch) return CLSLAM_OK;
+    DzPtrs dzp; for (int k = 0; k < 4; ++k) dzp.dz[k] = dz[k];
+    CLSLAM_REQUIRE(H % 8 == 0 && W % 8 == 0 && (size_t)batch * H * W < ((size_t)1 << 31), "disp_grad_pyramid: H, W must be multiples of 8");
+    hipLaunchKernelGGL(disp_grad_coop_kernel, dim3(cdiv(batch * H * W, 256), 4), dim3(256), 0, (hipStream_t)stream, ddisp_up,
+                       smooth_aux, n_smooth, batch, H, W, make_pyramid(disp, H, W), dzp);
+    return check_launch("disp_grad_pyramid");
 }
 
 

@@ -20,8 +20,6 @@ candidates, the propagated rounding of the SSIM variances for the clamp flag); a
 fails, and differing cells / selections are capped at 0.1 % of the pixels of a case (asserted for the fp32 restatement
 before the kernel is compared).
 
-`loss_bwd_pyramid` is exposed by ops but called by nothing in the engine; it is tested here like its twin loss_bwd2_pyramid.
-
 Measured figures (kernel | torch fp32, against float64), emu = kernel sources on the CPU emulator, hip = gfx950:
 the worst case over all cases and scales of each quantity (every row is printed per case when the tests run with -s):
   quantity                                   emu kernel | fp32   (ratio)     hip kernel | fp32   (ratio)
@@ -43,15 +41,14 @@ the worst case over all cases and scales of each quantity (every row is printed 
   loss_bwd2 ddisp_up max                       7.85e-09 | 3.81e-09 (2.06x)     7.82e-09 | 5.26e-09 (1.49x)
   loss_bwd2 dP sums max                        1.90e-08 | 6.14e-09 (3.09x)     1.46e-07 | 4.38e-08 (3.33x)
   loss_bwd2 dP sums rel L2                     5.79e-07 | 1.88e-07 (3.08x)     1.08e-06 | 3.85e-07 (2.81x)
-  loss_bwd (unused twin) dP sums max           3.35e-07 | 1.92e-07 (1.74x)     1.37e-07 | 7.59e-08 (1.81x)
   photo_grad dpred max                         4.22e-10 | 4.22e-10 (1.00x)     6.12e-10 | 6.12e-10 (1.00x)
   warp_bwd ddisp_up max                        8.09e-09 | 3.81e-09 (2.12x)     7.88e-09 | 5.26e-09 (1.50x)
   warp_bwd dP sums max                         1.90e-08 | 6.14e-09 (3.09x)     1.44e-07 | 7.59e-08 (1.90x)
   disp_grad dz max                             1.97e-09 | 1.74e-09 (1.13x)     5.50e-10 | 4.34e-10 (1.27x)
   disp_grad_pyramid dz max                     2.91e-10 | 3.82e-10 (0.76x)     2.91e-10 | 3.82e-10 (0.76x)
   pose_bwd dpose max (|ref| 2.5e+04)           4.88e-04 | 1.38e-01 (0.004x)    4.88e-04 | 1.38e-01 (0.004x)
-photo_grad / loss_bwd: before photo_grad_px summed alpha + beta x + gamma y per neighbour (csrc/loss.hip) the emulator gave
-photo_grad dpred 3.45e-09 | 3.87e-10 (8.9x) and loss_bwd dP sums 1.25e-07 | 2.94e-08 (4.25x): the two checks that failed.
+photo_grad: before photo_grad_px summed alpha + beta x + gamma y per neighbour (csrc/loss.hip) the emulator gave
+photo_grad dpred 3.45e-09 | 3.87e-10 (8.9x): the check that failed.
 
 One-line mutations of the kernels (CPU emulator, scratch copies) and the test of this file that fails; "before" = whether
 test_loss_stage.py (as it was), test_backward_parity.py and test_warp_positions.py caught it on the emulator:
@@ -684,7 +681,7 @@ SAMPLE_W = {2: (0.65, 0.35), 3: (0.5, 0.3, 0.2)}
 @pytest.mark.parametrize('backend', BACKENDS)
 @pytest.mark.parametrize('B,H,W,mode,motion', WARP_CASES)
 def test_loss_backward(backend, B, H, W, mode, motion, capsys):
-    """loss_bwd2_pyramid, its unused twin loss_bwd_pyramid and the single-scale pair photo_grad + warp_bwd on the same
+    """loss_bwd2_pyramid and the single-scale pair photo_grad + warp_bwd on the same
     constructed inputs: sel by _selection, coef_sel from the float64 reference rounded to fp32 (NaN where nothing may be
     read), warped = the float64 warp rounded to fp32, non-uniform sample weights, the cases of test_warp_fwd (W = 96 / 160,
     20x70 with H % 8 = 4, depth modes 0 / 1 / 2, a band of samples leaving on each side, den < 0).
@@ -706,7 +703,7 @@ def test_loss_backward(backend, B, H, W, mode, motion, capsys):
     refs = [(_reference_backward(sc, s, sel[s], coef_sel[s], warped[s], sw, kcells[s], F64),
              _reference_backward(sc, s, sel[s], coef_sel[s], warped[s], sw, kcells[s], F32)) for s in range(4)]
     args = (t(warped), t(sc['target']), t(sc['src_m1']), t(sc['src_p1']), t(sc['Kinv']), t(sc['P']), t(sw))
-    # --- loss_bwd2_pyramid (twice) and loss_bwd_pyramid
+    # --- loss_bwd2_pyramid (twice)
     nb2 = ops.loss_bwd2_blocks(H, W)
     runs = []
     for _ in range(2):
@@ -715,19 +712,14 @@ def test_loss_backward(backend, B, H, W, mode, motion, capsys):
         ops.loss_bwd2_pyramid(disps_d, t(sel), t(coef_sel), *args, dd, dpp, *sc['depths'])
         runs.append((dd.cpu(), dpp.cpu()))
     assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
-    nb1 = ops.loss_bwd_blocks(H, W)
     coef2 = torch.stack([torch.where((sel == 2 + fi)[:, :, None], coef_sel, torch.full_like(coef_sel, NAN)) for fi in range(2)], 1)
-    dd1 = torch.full((4, B, H, W), NAN, device=dev)
-    dpp1 = torch.full((4, B, nb1, 24), NAN, dtype=F64, device=dev)
-    ops.loss_bwd_pyramid(disps_d, t(sel), t(coef2), *args, dd1, dpp1, *sc['depths'])
     # --- single scale: photo_grad + warp_bwd
     nbw = ops.warp_bwd_blocks(H, W)
     for s in range(4):
         (g64, dd64, dP64), (g32, dd32, dP32) = refs[s]
         assert float(dd64.abs().max()) > 0 and float(dP64.abs().max()) > 0
-        for kname, kdd, kdp in (('loss_bwd2', runs[0][0][s], runs[0][1][s]), ('loss_bwd', dd1[s], dpp1[s])):
-            _measured(backend, name + f' s{s}', kname + ' ddisp_up', kdd, dd64, dd32)
-            _measured(backend, name + f' s{s}', kname + ' dP sums', kdp.cpu().sum(1), dP64, dP32)
+        _measured(backend, name + f' s{s}', 'loss_bwd2 ddisp_up', runs[0][0][s], dd64, dd32)
+        _measured(backend, name + f' s{s}', 'loss_bwd2 dP sums', runs[0][1][s].sum(1), dP64, dP32)
         dpred = torch.full((2, B, 3, H, W), NAN, device=dev)
         ops.photo_grad(t(sel[s]), t(coef2[s]), t(warped[s]), *args[1:2], t(sw), dpred, B, H, W)
         _measured(backend, name + f' s{s}', 'photo_grad dpred', dpred, g64, g32)
@@ -743,7 +735,7 @@ def test_loss_backward(backend, B, H, W, mode, motion, capsys):
 @pytest.mark.parametrize('B,H,W', [(3, 32, 96), (2, 20, 70)])
 def test_identity_selection_gives_exact_zero(backend, B, H, W):
     """sel all 0 / 1 (the automask won everywhere): every element of ddisp_up and of the pose-gradient partials is written,
-    and is exactly 0, by all three backward paths; coef_sel is NaN throughout (nothing may be read from it)."""
+    and is exactly 0, by loss_bwd2_pyramid and by the single-scale pair photo_grad + warp_bwd; coef_sel is NaN throughout (nothing may be read from it)."""
     dev = use_backend(backend)
     sc = _scene(12, B, H, W, 1, 'small')
     sw = torch.tensor(SAMPLE_W[B])
@@ -756,11 +748,7 @@ def test_identity_selection_gives_exact_zero(backend, B, H, W):
     dpp = torch.full((4, B, ops.loss_bwd2_blocks(H, W), 24), NAN, dtype=F64, device=dev)
     ops.loss_bwd2_pyramid(disps_d, t(sel), t(coef_sel), *args, dd, dpp, *sc['depths'])
     assert float(dd.abs().max()) == 0.0 and float(dpp.abs().max()) == 0.0
-    dd = torch.full((4, B, H, W), NAN, device=dev)
-    dpp = torch.full((4, B, ops.loss_bwd_blocks(H, W), 24), NAN, dtype=F64, device=dev)
     coef2 = torch.full((4, 2, B, 9, H, W), NAN)
-    ops.loss_bwd_pyramid(disps_d, t(sel), t(coef2), *args, dd, dpp, *sc['depths'])
-    assert float(dd.abs().max()) == 0.0 and float(dpp.abs().max()) == 0.0
     dpred = torch.full((2, B, 3, H, W), NAN, device=dev)
     ops.photo_grad(t(sel[1]), t(coef2[1]), t(warped[1]), t(sc['target']), t(sw), dpred, B, H, W)
     assert float(dpred.abs().max()) == 0.0
