@@ -48,6 +48,20 @@ class LossDesc(C.Structure):
                 ('smooth_scale', C.c_float), ('vel_scale', C.c_float)]
 
 
+STORE_MAX_PLANES = 16
+
+
+class StorePackDesc(C.Structure):
+    _fields_ = [('plane', fptr * STORE_MAX_PLANES), ('offset', i32 * STORE_MAX_PLANES), ('count', i32 * STORE_MAX_PLANES),
+                ('n_planes', i32)]
+
+
+class StoreGatherDesc(C.Structure):
+    _fields_ = [('rgb', fptr * STORE_MAX_PLANES), ('aug', fptr * STORE_MAX_PLANES), ('stride', C.c_int64 * STORE_MAX_PLANES),
+                ('offset', i32 * STORE_MAX_PLANES), ('h', i32 * STORE_MAX_PLANES), ('w', i32 * STORE_MAX_PLANES),
+                ('n_frames', i32), ('n_levels', i32), ('capacity', i32), ('slot_bytes', C.c_int64)]
+
+
 # name -> argtypes (restype is always int unless listed in _RESTYPES)
 _SIGNATURES = {
     'clslam_version': [],
@@ -118,6 +132,8 @@ _SIGNATURES = {
                                C.POINTER(C.c_double), C.c_void_p],
     'clslam_color_jitter_f32_blocks': [i32, i32],
     'clslam_color_jitter_f32': [fptr, fptr, C.c_void_p, fptr, i32, i32, i32, C.c_void_p],
+    'clslam_store_pack': [C.POINTER(StorePackDesc), C.c_void_p, C.c_void_p, C.c_void_p],
+    'clslam_store_gather_jitter': [C.POINTER(StoreGatherDesc), C.c_void_p, C.c_void_p, C.c_void_p, fptr, i32, i32, C.c_void_p],
     'clslam_avgpool_chunks': [i32],
     'clslam_global_avgpool': [fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
     'clslam_se_gate': [fptr, fptr, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
@@ -152,7 +168,7 @@ _SIGNATURES = {
     'clslam_pcl_resolve': [fptr, fptr, C.c_longlong, fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
-ABI_VERSION = 107          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
+ABI_VERSION = 108          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32]}      # return size_t
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}

@@ -11,11 +11,12 @@ by the library's host function and kept on the device; the kernels are integer m
 contrast / saturation / hue adjustments of PIL images in a drawn order) with Pillow's arithmetic, also bit-exact.
 """
 import ctypes as C
-from typing import Dict, Sequence, Tuple
+import os
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import _p, _pa, _stream
 
 
@@ -152,6 +153,122 @@ def draw_color_jitter(brightness=(0.8, 1.2), contrast=(0.8, 1.2), saturation=(0.
     return order, factors
 
 
+class FrameStore:
+    """Device-resident uint8 store of whole replay samples (include/clslam_hip.h, clslam_store_*).  When ``ReplayBuffer.add``
+    (slam/replay_buffer.py:82-184) sees a sample, that sample already holds the un-augmented pyramid ``_get`` later rebuilds from
+    the PNGs (replay_buffer.py:270-279 runs the dataset's own chain, datasets/kitti.py:249-259, datasets/utils.py:154-171): every
+    value is fl32(b / 255) of a byte b, so the bytes are all a replayed sample needs.
+
+    One slot = one sample: per frame (in ``frames`` order) and level (in ``scales`` order) a planar (3, H>>s, W>>s) uint8 block at
+    a fixed offset (rounded up to 16 bytes).  ``store_bytes // slot_bytes`` slots, one tensor allocated on first use; keyed by the
+    sample's .pkl file name; when full the OLDEST slot is reused (its sample falls back to the PNG path).  The pickled non-image
+    entries of every sample stay on the host: a hit opens no file at all.  Every kernel runs on the caller's current stream: a
+    slot is packed, reused and gathered on that one stream, so reuse needs no further ordering."""
+
+    def __init__(self, height: int, width: int, scales: Sequence[int] = (0, 1, 2, 3), frames: Sequence[int] = (0, -1, 1),
+                 store_bytes: int = 0, device=None) -> None:
+        self.height, self.width, self.scales, self.frames = int(height), int(width), tuple(scales), tuple(frames)
+        if len(self.scales) * len(self.frames) > _lib.STORE_MAX_PLANES:
+            raise _lib.ClslamError(f'FrameStore: {len(self.frames)} frames x {len(self.scales)} levels, at most {_lib.STORE_MAX_PLANES}')
+        self.device = torch.device('cuda' if device is None else device)
+        self.sizes = [(self.height >> s, self.width >> s) for s in self.scales]
+        self.offsets, off = [], 0                       # [frame index * levels + level index] -> bytes from the slot's start
+        for _ in self.frames:
+            for h, w in self.sizes:
+                self.offsets.append(off)
+                off += (3 * h * w + 15) // 16 * 16
+        self.slot_bytes = off
+        self.capacity = int(store_bytes) // self.slot_bytes
+        self._data: Optional[torch.Tensor] = None
+        self._stage: Optional[torch.Tensor] = None
+        self._inexact: Optional[torch.Tensor] = None
+        self._slots: Dict[str, int] = {}                # key -> slot, oldest first (dicts keep insertion order)
+        self._free = list(range(self.capacity - 1, -1, -1))
+        self._entries: Dict[str, Dict] = {}
+
+    @staticmethod
+    def key_of(filename) -> str:
+        return os.fspath(filename)
+
+    def __contains__(self, key) -> bool:
+        return self.key_of(key) in self._slots
+
+    def __len__(self) -> int:
+        return len(self._slots)
+
+    def _allocate(self) -> None:
+        if self._data is None:
+            self._data = torch.zeros(self.capacity * self.slot_bytes, dtype=torch.uint8, device=self.device)
+            self._stage = torch.empty(self.slot_bytes, device=self.device)          # float staging of one sample's host planes
+            self._inexact = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def add_sample(self, key, sample: Dict, entries: Optional[Dict] = None) -> bool:
+        """Keep the ``('rgb', frame, scale)`` planes of `sample` (host tensors, pinned or not, or device tensors; (1,3,h,w) or
+        (3,h,w) float32) under `key`, the sample's .pkl file.  `entries`: its non-image entries; None = read them from that file,
+        once, now.  -> False when the store has no slot at all (then nothing is kept)."""
+        key = self.key_of(key)
+        if self.capacity <= 0:
+            return False
+        self._allocate()
+        planes = []
+        for fi, frame in enumerate(self.frames):
+            for li, s in enumerate(self.scales):
+                t, (h, w) = sample['rgb', frame, s], self.sizes[li]
+                if t.dtype != torch.float32 or t.numel() != 3 * h * w or tuple(t.shape[-3:]) != (3, h, w):
+                    raise _lib.ClslamError(f"FrameStore.add_sample: ('rgb', {frame}, {s}) is {tuple(t.shape)} {t.dtype}, expected "
+                                           f'(1, 3, {h}, {w}) float32')
+                if t.device != self._data.device or not t.is_contiguous():
+                    o = self.offsets[fi * len(self.scales) + li]                 # floats here, bytes in the slot: 16-byte aligned
+                    staged = self._stage[o:o + 3 * h * w]
+                    staged.view(t.shape).copy_(t, non_blocking=True)             # one asynchronous copy per plane
+                    t = staged
+                planes.append(t)
+        if entries is None:
+            import pickle
+            with open(key, 'rb') as f:
+                entries = pickle.load(f)
+        entries = {k: v.clone() if isinstance(v, torch.Tensor) else v for k, v in entries.items()
+                   if not (isinstance(k, tuple) and k[0] in ('rgb', 'rgb_aug'))}                      # ('rgb', frame): the PNG's path
+        slot = self._slots.pop(key, None)
+        if slot is None:
+            if not self._free:
+                oldest = next(iter(self._slots))
+                self._free.append(self._slots.pop(oldest))
+                del self._entries[oldest]
+            slot = self._free.pop()
+        ops.store_pack(planes, self.offsets, self._data[slot * self.slot_bytes:(slot + 1) * self.slot_bytes], self._inexact)
+        self._slots[key], self._entries[key] = slot, entries
+        return True
+
+    def drop(self, key) -> None:
+        key = self.key_of(key)
+        slot = self._slots.pop(key, None)
+        if slot is not None:
+            self._free.append(slot)
+            del self._entries[key]
+
+    def entries(self, key) -> Dict:
+        """a fresh copy of the sample's non-image entries (`_get` changes its dict, replay_buffer.py:286-290)"""
+        return {k: v.clone() if isinstance(v, torch.Tensor) else v for k, v in self._entries[self.key_of(key)].items()}
+
+    def slot_of(self, key) -> int:
+        return self._slots.get(self.key_of(key), -1)
+
+    def inexact_pixels(self) -> int:
+        """values packed so far that were no byte / 255 (0 for samples a dataset built).  Debug / test read: it synchronises."""
+        return 0 if self._inexact is None else int(self._inexact.item())
+
+    def gather(self, keys, params: Optional[torch.Tensor], rgb, aug, row0: int = 0) -> None:
+        """rows row0 + i of the (rows, 3, h, w) tensors rgb[frame index * levels + level index] (and aug, with the jitter of
+        params = jitter_params(...), one record per IMAGE; aug None: no jitter) <- the sample stored under keys[i]; a key that is
+        None or not in the store leaves its rows untouched."""
+        slots = [-1 if k is None else self.slot_of(k) for k in keys]
+        if self._data is None or all(v < 0 for v in slots):
+            return
+        idx = torch.tensor([v for v in slots for _ in self.frames], dtype=torch.int32).to(self._data.device, non_blocking=True)
+        ops.store_gather_jitter(self._data, self.slot_bytes, self.offsets, self.sizes, len(self.frames), idx, params, rgb, aug, row0)
+
+
 class ReplaySampleBuilder:
     """What ``ReplayBuffer._get`` (slam/replay_buffer.py:263-291) builds per replayed sample -- PNG -> RGB, the LANCZOS pyramid level
     from level, ToTensor, one drawn colour jitter on every level -- with the pixels on the GPU: the host decodes the PNGs
@@ -167,10 +284,15 @@ class ReplaySampleBuilder:
 
     def __init__(self, height: int, width: int, scales: Sequence[int] = (0, 1, 2, 3), frames: Sequence[int] = (0, -1, 1),
                  device=None, do_augmentation: bool = True, cache_frames: int = 0, cache_bytes: int = 256 << 20,
-                 decode_threads: int = 16) -> None:
+                 decode_threads: int = 16, store_bytes: int = 0) -> None:
         self.height, self.width, self.scales, self.frames = int(height), int(width), tuple(scales), tuple(frames)
         self.device = torch.device('cuda' if device is None else device)
         self.do_augmentation = bool(do_augmentation)
+        # opt-in: keep the samples themselves as bytes in device memory (FrameStore): a sample seen by `add`, or decoded once,
+        # is served without its PNGs.  0: no store, everything below behaves as without this argument.
+        self.store = FrameStore(height, width, self.scales, self.frames, store_bytes, self.device) if store_bytes > 0 else None
+        if self.store is not None and self.store.capacity < 1:
+            raise _lib.ClslamError(f'store_bytes = {store_bytes} holds no sample ({self.store.slot_bytes} bytes each)')
         self.pyramid = ImagePyramid(height, width, tuple(range(max(self.scales) + 1)))
         # opt-in: keep the DECODED uint8 frames of the last `cache_frames` image files on the host (a replay buffer re-serves
         # the same few hundred samples: a 1241x376 PNG costs ~7 ms to decode, its 1.4 MB cost nothing to keep).  Bounded by
@@ -195,11 +317,20 @@ class ReplaySampleBuilder:
           per file, the sampler draws from its own numpy generator before any of them), so a seeded run consumes the same
           random streams.
         * ``replay_buffer._get`` (direct callers) becomes get_one.
+        * with ``store_bytes > 0`` and a buffer that has an ``add``: ``replay_buffer.add`` still runs the reference's own add, then
+          the file names that appeared in / vanished from ``online_filenames`` are added to / dropped from the frame store (the
+          online sample holds the very planes `_get` would rebuild from the PNGs -- as long as the online dataset neither flips
+          nor jitters its 'rgb' entries, which the reference's driver does not).
+        Calling install() again is harmless: the buffer's own methods are kept on the buffer and wrapped afresh.
         * ``slam._cat_dict`` (slam/slam.py:300-309 joins the online sample, host tensors, with the replay minibatch) becomes
           cat_dict below: torch.cat refuses mixed devices, the online entries are uploaded first.
         """
         builder = self
-        reference_get = replay_buffer.get
+        # the buffer's own bound methods are kept ON the buffer: a second install() (of this or another builder) wraps them, not
+        # the wrappers of the first
+        if not hasattr(replay_buffer, '_clslam_reference_get'):
+            replay_buffer._clslam_reference_get = replay_buffer.get
+        reference_get = replay_buffer._clslam_reference_get
         replay_buffer._get = self.get_one
 
         def get(*args, **kwargs):
@@ -215,6 +346,8 @@ class ReplaySampleBuilder:
                 replay_buffer._get = builder.get_one
             if not names:
                 return stub
+            if builder.store is not None and names[0][1]:
+                return builder.get_batch([n for n, _ in names])
             datas = builder.get_many([n for n, _ in names], include_batch=names[0][1])
             out = datas[0]
             for data in datas[1:]:
@@ -222,9 +355,38 @@ class ReplaySampleBuilder:
                     out[key] = torch.cat([out[key], data[key]])
             return out
         replay_buffer.get = get
+        if self.store is not None and (hasattr(replay_buffer, 'add') or hasattr(replay_buffer, '_clslam_reference_add')):
+            if not hasattr(replay_buffer, '_clslam_reference_add'):
+                replay_buffer._clslam_reference_add = replay_buffer.add
+            reference_add = replay_buffer._clslam_reference_add
+
+            def add(sample, *args, **kwargs):
+                # the reference's own add, unchanged (replay_buffer.py:82-184); what it did shows in online_filenames
+                before = list(replay_buffer.online_filenames)
+                out = reference_add(sample, *args, **kwargs)
+                after = list(replay_buffer.online_filenames)
+                for fn in before:
+                    if fn not in after:
+                        builder.store.drop(fn)
+                for fn in after:
+                    if fn not in before and builder._has_planes(sample):
+                        builder.store.add_sample(fn, sample)
+                return out
+            replay_buffer.add = add
+        elif hasattr(replay_buffer, '_clslam_reference_add'):          # a builder without a store after one with a store
+            replay_buffer.add = replay_buffer._clslam_reference_add
         if slam is not None:
             slam._cat_dict = cat_dict
         return self
+
+    def close(self) -> None:
+        """shut the PNG decode pool down (idle threads otherwise live as long as the builder)"""
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+    def _has_planes(self, sample) -> bool:
+        return all(('rgb', f, s) in sample for f in self.frames for s in self.scales)
 
     def _decode_file(self, path):
         import numpy as np
@@ -265,7 +427,18 @@ class ReplaySampleBuilder:
         """-> one dict per file, exactly the entries `_get(filename, include_batch)` returns."""
         import pickle
 
-        import numpy as np
+        if self.store is not None:
+            keys, whole, singles = self._build_batch(filenames, rng)
+            datas = []
+            for i, single in enumerate(singles):
+                data = dict(single)
+                for k in keys:
+                    data[k] = whole[k][1 + i:2 + i] if include_batch else whole[k][1 + i]
+                if not include_batch:                                # replay_buffer.py:286-289
+                    for key in single:
+                        data[key] = data[key].squeeze(0)
+                datas.append(data)
+            return datas
         datas, paths, draws = [], [], []
         for fn in filenames:
             # the jitter is drawn BEFORE the file is read (replay_buffer.py:264-268): same random stream as the reference
@@ -305,18 +478,121 @@ class ReplaySampleBuilder:
                         data[key] = data[key].squeeze(0)
         return datas
 
+    def _build_batch(self, filenames, rng=None):
+        """The K samples of `filenames` through the frame store -> (image keys in `_get`'s order, {key: (1 + K, 3, h, w) tensor
+        whose rows 1.. are the samples}, the K dicts of non-image entries).  Hits are gathered from the store by two launches;
+        misses take the PNG path, are copied into their rows and packed into the store (decoded at most once)."""
+        import pickle
+        store, K, nf = self.store, len(filenames), len(self.frames)
+        singles, miss, draws = [], [], []
+        for i, fn in enumerate(filenames):
+            # the jitter is drawn first, hit or miss (replay_buffer.py:264-268): Python's random stream is the reference's
+            draw = draw_color_jitter(rng=rng) if self.do_augmentation else None
+            draws.extend([draw] * nf)
+            if fn in store:
+                singles.append(store.entries(fn))
+            else:
+                with open(fn, 'rb') as f:
+                    data = pickle.load(f)
+                miss.append((i, fn, [data.pop(('rgb', frame)) for frame in self.frames]))
+                singles.append(data)
+        # ONE allocation for the batch; every key is a contiguous (1 + K, 3, h, w) piece of it
+        sizes = store.sizes
+        per_row = sum(3 * h * w for h, w in sizes) * nf
+        n_kinds = 2 if self.do_augmentation else 1
+        block = torch.empty(n_kinds * (1 + K) * per_row, device=self.device)
+        pieces, at = [], 0
+        for _ in range(n_kinds * nf):
+            for h, w in sizes:
+                n = (1 + K) * 3 * h * w
+                pieces.append(block[at:at + n].view(1 + K, 3, h, w))
+                at += n
+        rgb, aug = pieces[:nf * len(sizes)], (pieces[nf * len(sizes):] if self.do_augmentation else None)
+        params = jitter_params(draws, self.device) if self.do_augmentation else None
+        missed = {i for i, _, _ in miss}
+        store.gather([None if i in missed else fn for i, fn in enumerate(filenames)], params, rgb, aug, row0=1)
+        if miss:
+            raws = self._decode_all([p for _, _, paths in miss for p in paths])
+            if len({tuple(r.shape) for r in raws}) != 1:
+                raise _lib.ClslamError('replay samples with different raw image sizes in one batch')
+            stage = torch.empty((len(raws),) + tuple(raws[0].shape), dtype=torch.uint8, device=self.device)
+            for i, r in enumerate(raws):
+                stage[i].copy_(r, non_blocking=True)
+            levels = self.pyramid(stage)
+            if self.do_augmentation:
+                pick = torch.tensor([i * nf + j for i, _, _ in miss for j in range(nf)], device=self.device)
+                miss_params = params.view(-1, 48)[pick].reshape(-1)
+                jit = {s: color_jitter_tensor(levels[s], miss_params) for s in self.scales}
+            rows = torch.tensor([1 + i for i, _, _ in miss], device=self.device)
+            for j in range(nf):
+                for li, s in enumerate(self.scales):
+                    rgb[j * len(sizes) + li].index_copy_(0, rows, levels[s][j::nf])
+                    if self.do_augmentation:
+                        aug[j * len(sizes) + li].index_copy_(0, rows, jit[s][j::nf])
+            for m, (i, fn, _) in enumerate(miss):                      # after the gather (same stream): a reused slot was read
+                store.add_sample(fn, {('rgb', frame, s): levels[s][m * nf + j] for j, frame in enumerate(self.frames)
+                                      for s in self.scales}, entries=singles[i])
+        keys, whole = [], {}
+        for j, frame in enumerate(self.frames):
+            for li, s in enumerate(self.scales):
+                t = j * len(sizes) + li
+                keys += [('rgb', frame, s), ('rgb_aug', frame, s)]
+                whole['rgb', frame, s] = rgb[t]
+                whole['rgb_aug', frame, s] = aug[t] if self.do_augmentation else rgb[t]
+        return keys, whole, singles
+
+    def get_batch(self, filenames, rng=None) -> Dict:
+        """What ``ReplayBuffer.get`` returns for `filenames` (replay_buffer.py:229-233: the K dicts of `_get` concatenated key by
+        key), with a frame store: every entry is rows 1.. of a freshly allocated (1 + K, ...) tensor, so that cat_dict() only has
+        to fill row 0 with the online sample.  New tensors on every call."""
+        if self.store is None:
+            datas = self.get_many(filenames, rng=rng)
+            return {k: torch.cat([d[k] for d in datas]) for k in datas[0]} if datas else {}
+        if not len(filenames):
+            return {}
+        keys, whole, singles = self._build_batch(filenames, rng)
+        out = {}
+        for k in singles[0]:
+            vals = [d[k] for d in singles]
+            v0 = vals[0]
+            if all(isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == 1 and v.shape == v0.shape and v.dtype == v0.dtype
+                   and v.device == v0.device for v in vals):
+                w = torch.empty((1 + len(vals),) + tuple(v0.shape[1:]), dtype=v0.dtype, device=v0.device)
+                torch.cat(vals, out=w[1:])
+                out[k] = _rows_of(w)
+            else:
+                out[k] = torch.cat(vals)
+        for k in keys:
+            out[k] = _rows_of(whole[k])
+        return out
+
     def get_one(self, filename, include_batch: bool = True):
         """``ReplayBuffer._get(filename, include_batch=True)``"""
         return self.get_many([filename], include_batch)[0]
 
 
+def _rows_of(whole: torch.Tensor) -> torch.Tensor:
+    """whole[1:], remembering the tensor it is cut from: cat_dict() fills row 0 instead of concatenating"""
+    rows = whole[1:]
+    rows._clslam_whole = whole
+    return rows
+
+
 def cat_dict(online: Dict, replay: Dict, device=None) -> Dict:
     """slam/slam.py:300-309 (`_cat_dict`) for a replay dict whose image tensors already live on the GPU: entries present in both
-    dicts are concatenated there (the online sample's entries are uploaded; torch.cat refuses mixed devices)."""
+    dicts are concatenated there (the online sample's entries are uploaded; torch.cat refuses mixed devices).  An entry that
+    get_batch() cut from a (1 + K, ...) tensor is not concatenated: the online entry is copied into row 0 and that tensor is
+    returned (it shares its rows 1.. with `replay`; a second cat_dict on the same `replay` overwrites row 0)."""
     out = {}
     for k in online:
         if k in replay:
             a, b = online[k], replay[k]
+            whole = getattr(b, '_clslam_whole', None)
+            if (whole is not None and a.shape[0] == 1 and a.shape[1:] == whole.shape[1:] and a.dtype == whole.dtype
+                    and whole.shape[0] == b.shape[0] + 1 and whole.data_ptr() + whole.stride(0) * whole.element_size() == b.data_ptr()):
+                whole[:1].copy_(a, non_blocking=True)
+                out[k] = whole if device is None or whole.device == torch.device(device) else whole.to(device, non_blocking=True)
+                continue
             dev = device if device is not None else (b.device if b.device.type != 'cpu' else a.device)
             out[k] = torch.cat([a.to(dev, non_blocking=True), b.to(dev, non_blocking=True)])
     return out

@@ -869,3 +869,51 @@ def pcl_to_image(points, K, image_shape, offsets=None, poses=None, min_z=None, r
             break
     extra = ([dist] if return_dist else []) + ([index] if return_index else [])
     return (image, *extra) if extra else image
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Frame store of the replay ingest (clslam_store_*, include/clslam_hip.h)
+def store_pack(planes, offsets, slot: torch.Tensor, inexact: torch.Tensor) -> None:
+    """planes: contiguous float tensors on the library's device (3 * h * w values each), written as bytes to slot[offsets[k]:];
+    `inexact` (int64, 1 element) counts the values that are no byte / 255."""
+    if len(planes) != len(offsets) or len(planes) > _lib.STORE_MAX_PLANES:
+        raise _lib.ClslamError(f'store_pack: {len(planes)} planes, {len(offsets)} offsets (at most {_lib.STORE_MAX_PLANES})')
+    desc = _lib.StorePackDesc()
+    desc.n_planes = len(planes)
+    for k, (t, off) in enumerate(zip(planes, offsets)):
+        if off < 0 or off + t.numel() > slot.numel():
+            raise _lib.ClslamError(f'store_pack: plane {k} ({t.numel()} bytes at {off}) leaves the slot ({slot.numel()} bytes)')
+        desc.plane[k], desc.offset[k], desc.count[k] = _p(t), int(off), t.numel()
+    _lib.get_lib().call('clslam_store_pack', C.byref(desc), _pa(slot, torch.uint8), _pa(inexact, torch.int64), _stream(slot))
+
+
+def store_gather_jitter(store: torch.Tensor, slot_bytes: int, offsets, sizes, n_frames: int, slot_idx: torch.Tensor,
+                        params: Optional[torch.Tensor], rgb, aug, row0: int) -> None:
+    """store (capacity * slot_bytes,) uint8; offsets[frame * n_levels + level] bytes inside a slot; sizes[level] = (h, w);
+    slot_idx (n_images,) int32, < 0 = skip; rgb / aug: per table entry a contiguous (rows, 3, h, w) float tensor (aug None: no
+    jitter), image i goes to row row0 + i // n_frames."""
+    n_levels, n_img = len(sizes), slot_idx.numel()
+    n_tab = n_frames * n_levels
+    if n_tab > _lib.STORE_MAX_PLANES or len(offsets) != n_tab or len(rgb) != n_tab or n_img % n_frames:
+        raise _lib.ClslamError(f'store_gather_jitter: {n_frames} frames x {n_levels} levels, {len(offsets)} offsets, {len(rgb)} outputs, '
+                               f'{n_img} images')
+    if aug is not None and (len(aug) != n_tab or params is None or params.numel() != n_img * 48):
+        raise _lib.ClslamError(f'store_gather_jitter: rgb_aug rows need {n_tab} outputs and 48 parameter bytes per image')
+    desc = _lib.StoreGatherDesc()
+    desc.n_frames, desc.n_levels, desc.slot_bytes = n_frames, n_levels, int(slot_bytes)
+    desc.capacity = store.numel() // int(slot_bytes)
+    rows_needed = row0 + n_img // n_frames
+    for li, (h, w) in enumerate(sizes):
+        desc.h[li], desc.w[li] = int(h), int(w)
+    for t in range(n_tab):
+        h, w = sizes[t % n_levels]
+        if offsets[t] < 0 or offsets[t] + 3 * h * w > slot_bytes:
+            raise _lib.ClslamError(f'store_gather_jitter: entry {t} leaves the slot')
+        for out in (rgb[t],) + (() if aug is None else (aug[t],)):
+            if out.dim() != 4 or tuple(out.shape[1:]) != (3, h, w) or out.shape[0] < rows_needed:
+                raise _lib.ClslamError(f'store_gather_jitter: entry {t} needs ({rows_needed}+, 3, {h}, {w}), got {tuple(out.shape)}')
+        desc.rgb[t], desc.aug[t] = _p(rgb[t]), None if aug is None else _p(aug[t])
+        desc.stride[t], desc.offset[t] = 3 * h * w, int(offsets[t])
+    partial = torch.empty(n_levels * max(n_img, 1) * 64, device=store.device) if aug is not None else None
+    _lib.get_lib().call('clslam_store_gather_jitter', C.byref(desc), _pa(store, torch.uint8), _pa(slot_idx, torch.int32),
+                        None if aug is None else _pa(params, torch.uint8), _p(partial), n_img, int(row0), _stream(store))

@@ -372,6 +372,12 @@ __device__ __forceinline__ void jitter_ops(const JitterParams& P, int k0, int k1
     }
 }
 
+// blocks per image of the gray-sum pass (its partition fixes the summation order of the contrast mean)
+__host__ __device__ inline int jitter_sum_blocks(int hw) {
+    const int n = (hw + 1023) / 1024;
+    return n < 1 ? 1 : (n > 64 ? 64 : n);
+}
+
 __device__ __forceinline__ int jitter_contrast_pos(const JitterParams& P) {
     for (int k = 0; k < 4; ++k) {
         if (P.order[k] < 0) break;
@@ -428,7 +434,7 @@ __global__ __launch_bounds__(256) void jitter_f32_apply_kernel(const float* __re
 
 }  // namespace clslam
 
-extern "C" int clslam_color_jitter_f32_blocks(int h, int w) { return std::max(1, std::min(64, clslam::cdiv(h * w, 1024))); }
+extern "C" int clslam_color_jitter_f32_blocks(int h, int w) { return clslam::jitter_sum_blocks(h * w); }
 
 extern "C" int clslam_color_jitter_f32(const float* src, float* dst, const void* params, float* partial, int n_images, int h, int w,
                                        void* stream_) {
@@ -443,4 +449,192 @@ extern "C" int clslam_color_jitter_f32(const float* src, float* dst, const void*
     hipLaunchKernelGGL(clslam::jitter_f32_apply_kernel, dim3(nb2, n_images), dim3(256), 0, stream, src, dst,
                        (const clslam::JitterParams*)params, partial, nblk, h * w);
     return clslam::check_launch("color_jitter_f32");
+}
+
+// =====================================================================================================================
+// Frame store: replayed samples served from HBM instead of from their PNGs.  When ReplayBuffer.add (slam/replay_buffer.py:82-184)
+// sees a sample, that sample already holds the un-augmented pyramid `_get` later rebuilds from the image files
+// (replay_buffer.py:270-279 runs the chain of datasets/kitti.py:249-259, datasets/utils.py:154-171): every value is fl32(b / 255) of
+// a byte b, and b = round(x * 255) recovers it.  A slot keeps those bytes: per frame and level one planar (3, h, w) block at a
+// fixed, 16-byte aligned offset.  clslam_store_pack fills a slot from float planes; clslam_store_gather_jitter turns slots back
+// into the rgb / rgb_aug rows of the minibatch (ToTensor with u8_to_planar_kernel's arithmetic, then the chain of
+// clslam_color_jitter_f32 with ITS summation order for the contrast mean: bitwise the same rgb_aug).
+namespace clslam {
+
+__device__ __forceinline__ unsigned store_byte(float x, unsigned& bad) {
+    const float q = fminf(fmaxf(rintf(x * 255.f), 0.f), 255.f);       // NaN -> 0 (and counted below)
+    const unsigned char b = (unsigned char)q;
+    bad += ((float)b / 255.f != x) ? 1u : 0u;
+    return b;
+}
+
+// grid (blocks, planes).  One plane = the 3 * h * w floats of one frame at one level.
+__global__ __launch_bounds__(256) void store_pack_kernel(clslam_store_pack_desc d, unsigned char* __restrict__ slot,
+                                                         unsigned long long* __restrict__ inexact) {
+    const int pl = blockIdx.y;
+    const float* __restrict__ src = d.plane[pl];
+    unsigned char* __restrict__ dst = slot + d.offset[pl];
+    const int n = d.count[pl];
+    const int nvec = (((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 3) == 0) ? n >> 2 : 0;
+    unsigned bad = 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) {
+        const float4 v = reinterpret_cast<const float4*>(src)[i];
+        const unsigned b0 = store_byte(v.x, bad), b1 = store_byte(v.y, bad), b2 = store_byte(v.z, bad), b3 = store_byte(v.w, bad);
+        reinterpret_cast<unsigned*>(dst)[i] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+    }
+    for (int i = 4 * nvec + blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) dst[i] = (unsigned char)store_byte(src[i], bad);
+    const float total = wave_sum((float)bad);          // small integers: exact
+    if ((threadIdx.x & 63) == 0 && total > 0.f) atomicAdd(inexact, (unsigned long long)total);
+}
+
+struct GatherImage {
+    const unsigned char* bytes;     // the (3, h, w) block of this image and level, nullptr: not served from the store
+    int hw, nblk, table;            // pixels, blocks of the sum pass, index into the descriptor's tables
+};
+
+__device__ __forceinline__ GatherImage gather_image(const clslam_store_gather_desc& d, const unsigned char* store,
+                                                    const int* slot_idx, int img, int li) {
+    GatherImage g;
+    const int slot = slot_idx[img];
+    g.table = (img % d.n_frames) * d.n_levels + li;
+    g.hw = d.h[li] * d.w[li];
+    g.nblk = jitter_sum_blocks(g.hw);
+    g.bytes = (slot < 0 || slot >= d.capacity) ? nullptr : store + (size_t)slot * d.slot_bytes + d.offset[g.table];
+    return g;
+}
+
+// grid (max sum blocks, images, levels); partial[level][image][64].  The partition of clslam_color_jitter_f32's sum pass: block b
+// of nblk, thread t takes the pixels b * 256 + t + k * nblk * 256.
+__global__ __launch_bounds__(256) void store_gather_sum_kernel(clslam_store_gather_desc d, const unsigned char* __restrict__ store,
+                                                               const int* __restrict__ slot_idx,
+                                                               const JitterParams* __restrict__ params, float* __restrict__ partial,
+                                                               int n_images) {
+    __shared__ float red[4];
+    const int img = blockIdx.y, li = blockIdx.z;
+    const GatherImage g = gather_image(d, store, slot_idx, img, li);
+    if (!g.bytes || (int)blockIdx.x >= g.nblk) return;
+    const JitterParams P = params[img];
+    const int kc = jitter_contrast_pos(P);
+    if (kc < 0) return;
+    const int hw = g.hw;
+    float acc = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < hw; i += g.nblk * 256) {
+        float r = (float)g.bytes[i] / 255.f, gg = (float)g.bytes[hw + i] / 255.f, b = (float)g.bytes[2 * hw + i] / 255.f;
+        jitter_ops(P, 0, kc, r, gg, b, 0.f);
+        acc += gray_of(r, gg, b);
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[((size_t)li * n_images + img) * 64 + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// grid (blocks, images, levels).  Four pixels per thread (one dword of bytes per colour plane in, one float4 per plane out)
+// where the block and both rows are aligned for it, one pixel per thread for the rest.
+__global__ __launch_bounds__(256) void store_gather_apply_kernel(clslam_store_gather_desc d, const unsigned char* __restrict__ store,
+                                                                 const int* __restrict__ slot_idx,
+                                                                 const JitterParams* __restrict__ params,
+                                                                 const float* __restrict__ partial, int n_images, int row0) {
+    __shared__ float s_mean;
+    const int img = blockIdx.y, li = blockIdx.z;
+    const GatherImage g = gather_image(d, store, slot_idx, img, li);
+    const int hw = g.hw;
+    if (!g.bytes || (int)blockIdx.x * 256 >= hw) return;
+    const bool jitter = d.aug[g.table] != nullptr;
+    JitterParams P;
+    P.order[0] = -1;
+    if (jitter) P = params[img];
+    if (threadIdx.x == 0) {
+        float m = 0.f;
+        if (jitter && jitter_contrast_pos(P) >= 0) {
+            const float* part = partial + ((size_t)li * n_images + img) * 64;
+            for (int k = 0; k < g.nblk; ++k) m += part[k];     // fixed order
+            m = m / (float)hw;
+        }
+        s_mean = m;
+    }
+    __syncthreads();
+    const float mean = s_mean;
+    const size_t row = (size_t)(row0 + img / d.n_frames) * (size_t)d.stride[g.table];
+    float* __restrict__ rgb = d.rgb[g.table] + row;
+    float* __restrict__ aug = jitter ? d.aug[g.table] + row : nullptr;
+    const bool aligned = (hw & 3) == 0 && ((uintptr_t)g.bytes & 3) == 0 && ((uintptr_t)rgb & 15) == 0 && ((uintptr_t)aug & 15) == 0;
+    const int nvec = aligned ? hw >> 2 : 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) {
+        const unsigned R = reinterpret_cast<const unsigned*>(g.bytes)[i], G = reinterpret_cast<const unsigned*>(g.bytes + hw)[i],
+                       B = reinterpret_cast<const unsigned*>(g.bytes + 2 * hw)[i];
+        float r[4], gg[4], b[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            r[j] = (float)((R >> (8 * j)) & 255u) / 255.f;
+            gg[j] = (float)((G >> (8 * j)) & 255u) / 255.f;
+            b[j] = (float)((B >> (8 * j)) & 255u) / 255.f;
+        }
+        reinterpret_cast<float4*>(rgb)[i] = make_float4(r[0], r[1], r[2], r[3]);
+        reinterpret_cast<float4*>(rgb + hw)[i] = make_float4(gg[0], gg[1], gg[2], gg[3]);
+        reinterpret_cast<float4*>(rgb + 2 * hw)[i] = make_float4(b[0], b[1], b[2], b[3]);
+        if (!jitter) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) jitter_ops(P, 0, 4, r[j], gg[j], b[j], mean);
+        reinterpret_cast<float4*>(aug)[i] = make_float4(r[0], r[1], r[2], r[3]);
+        reinterpret_cast<float4*>(aug + hw)[i] = make_float4(gg[0], gg[1], gg[2], gg[3]);
+        reinterpret_cast<float4*>(aug + 2 * hw)[i] = make_float4(b[0], b[1], b[2], b[3]);
+    }
+    for (int i = 4 * nvec + blockIdx.x * 256 + threadIdx.x; i < hw; i += gridDim.x * 256) {
+        float r = (float)g.bytes[i] / 255.f, gg = (float)g.bytes[hw + i] / 255.f, b = (float)g.bytes[2 * hw + i] / 255.f;
+        rgb[i] = r; rgb[hw + i] = gg; rgb[2 * hw + i] = b;
+        if (!jitter) continue;
+        jitter_ops(P, 0, 4, r, gg, b, mean);
+        aug[i] = r; aug[hw + i] = gg; aug[2 * hw + i] = b;
+    }
+}
+
+}  // namespace clslam
+
+extern "C" int clslam_store_pack(const clslam_store_pack_desc* desc, unsigned char* slot, unsigned long long* inexact, void* stream) {
+    CLSLAM_REQUIRE(desc && slot && inexact, "store_pack: null pointer");
+    CLSLAM_REQUIRE(desc->n_planes >= 0 && desc->n_planes <= CLSLAM_STORE_MAX_PLANES, "store_pack: %d planes (at most %d)",
+                   desc->n_planes, CLSLAM_STORE_MAX_PLANES);
+    int most = 0;
+    for (int k = 0; k < desc->n_planes; ++k) {
+        CLSLAM_REQUIRE(desc->plane[k] && desc->offset[k] >= 0 && desc->count[k] > 0, "store_pack: bad plane %d", k);
+        most = std::max(most, desc->count[k]);
+    }
+    if (desc->n_planes == 0) return CLSLAM_OK;
+    const int blocks = std::max(1, std::min(256, clslam::cdiv(most, 4 * 256)));
+    hipLaunchKernelGGL(clslam::store_pack_kernel, dim3(blocks, desc->n_planes), dim3(256), 0, (hipStream_t)stream, *desc, slot, inexact);
+    return clslam::check_launch("store_pack");
+}
+
+extern "C" int clslam_store_gather_jitter(const clslam_store_gather_desc* desc, const unsigned char* store, const int* slot_idx,
+                                          const void* params, float* partial, int n_images, int row0, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_images == 0) return CLSLAM_OK;
+    CLSLAM_REQUIRE(desc && store && slot_idx, "store_gather_jitter: null pointer");
+    CLSLAM_REQUIRE(n_images > 0 && n_images <= 65535 && row0 >= 0, "store_gather_jitter: bad geometry");
+    CLSLAM_REQUIRE(desc->n_frames >= 1 && desc->n_levels >= 1 && desc->n_frames * desc->n_levels <= CLSLAM_STORE_MAX_PLANES,
+                   "store_gather_jitter: %d frames x %d levels (at most %d planes)", desc->n_frames, desc->n_levels,
+                   CLSLAM_STORE_MAX_PLANES);
+    CLSLAM_REQUIRE(n_images % desc->n_frames == 0 && desc->capacity >= 1 && desc->slot_bytes > 0,
+                   "store_gather_jitter: %d images are no whole samples of %d frames, or an empty store", n_images, desc->n_frames);
+    bool jitter = false;
+    int most = 1, nblk = 1;
+    for (int li = 0; li < desc->n_levels; ++li) {
+        CLSLAM_REQUIRE(desc->h[li] > 0 && desc->w[li] > 0 && (size_t)desc->h[li] * desc->w[li] < ((size_t)1 << 29),
+                       "store_gather_jitter: bad size of level %d", li);
+        most = std::max(most, desc->h[li] * desc->w[li]);
+        nblk = std::max(nblk, clslam::jitter_sum_blocks(desc->h[li] * desc->w[li]));
+    }
+    for (int t = 0; t < desc->n_frames * desc->n_levels; ++t) {
+        CLSLAM_REQUIRE(desc->rgb[t] && desc->offset[t] >= 0 && desc->stride[t] > 0, "store_gather_jitter: bad table entry %d", t);
+        jitter = jitter || desc->aug[t];
+    }
+    CLSLAM_REQUIRE(!jitter || (params && partial), "store_gather_jitter: rgb_aug rows without parameters or scratch");
+    if (jitter)
+        hipLaunchKernelGGL(clslam::store_gather_sum_kernel, dim3(nblk, n_images, desc->n_levels), dim3(256), 0, stream, *desc, store,
+                           slot_idx, (const clslam::JitterParams*)params, partial, n_images);
+    const int nb2 = std::max(1, std::min(256, clslam::cdiv(most, 4 * 256)));
+    hipLaunchKernelGGL(clslam::store_gather_apply_kernel, dim3(nb2, n_images, desc->n_levels), dim3(256), 0, stream, *desc, store,
+                       slot_idx, (const clslam::JitterParams*)params, partial, n_images, row0);
+    return clslam::check_launch("store_gather_jitter");
 }

@@ -41,9 +41,9 @@ extern "C" {
 /* ABI version: 101 = clslam_conv_desc.weight_wino appended, clslam_wino_weight_*; 100 -> 101 also covers the double* dp_partial of
  * the view-synthesis / loss backward and clslam_pose_bwd (round 4); 102 = clslam_conv_desc.cu_limit appended; 103 = clslam_handoff_* added;
  * 104 = per-scale range forms of the four pyramid launches added; 105 = clslam_depth_metrics* added; 106 = clslam_pcl_* added;
- * 107 = the range forms of 104 and the unfused pyramid backward removed.
+ * 107 = the range forms of 104 and the unfused pyramid backward removed; 108 = clslam_store_* added (frame store).
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 107
+#define CLSLAM_ABI_VERSION 108
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -423,6 +423,45 @@ int clslam_color_jitter_u8(const unsigned char* src, unsigned char* dst, unsigne
 int clslam_color_jitter_f32_blocks(int h, int w);
 int clslam_color_jitter_f32(const float* src, float* dst, const void* params, float* partial, int n_images, int h, int w,
                             void* stream);
+
+/* Frame store: replayed samples kept as bytes in device memory instead of being rebuilt from their image files.  The sample that
+ * ReplayBuffer.add receives (slam/replay_buffer.py:82-184) already holds the un-augmented pyramid `_get` builds later
+ * (replay_buffer.py:270-279 = datasets/kitti.py:249-259, datasets/utils.py:154-171: Image.open -> LANCZOS level from level ->
+ * ToTensor), every value fl32(b / 255) of a byte b.  One SLOT of the store holds one sample: per frame and per level a planar
+ * (3, h, w) uint8 block at a fixed offset (a multiple of 16 bytes) inside the slot; table index = frame * n_levels + level.
+ *
+ * clslam_store_pack (one launch per sample) replaces nothing of the reference -- it is what lets the two entries below skip
+ * replay_buffer.py:268-279: plane[k] = the 3 * h * w floats of table entry k (device memory), written to slot + offset[k] as
+ * b = (unsigned char)rintf(x * 255); *inexact (device counter) grows by the number of values with (float)b / 255.f != x, which
+ * stays 0 for planes a dataset built.
+ *
+ * clslam_store_gather_jitter replaces, for samples in the store, replay_buffer.py:268-285 (pickle + Image.open + resize chain +
+ * ToTensor + colour jitter): image i (sample i / n_frames, frame i % n_frames) is read from slot slot_idx[i] (device array of
+ * n_images entries; < 0 or >= capacity: the image is skipped, its rows stay untouched) and written to row row0 + i / n_frames of
+ * the caller's (rows, 3, h, w) batch tensors: rgb[k] = byte / 255 (clslam_u8_to_planar_f32's arithmetic), aug[k] = the chain of
+ * clslam_color_jitter_f32 on it with params[i] (same 48-byte records), BITWISE what that entry point returns for the same
+ * bytes (same partition and order of the contrast mean's sum).  aug[k] == NULL: no jitter for that entry (params, partial may
+ * then be NULL).  stride[k]: floats between two rows of entry k.  partial: n_levels * n_images * 64 floats of scratch.  Two
+ * launches for all images and levels.                                                                                        */
+#define CLSLAM_STORE_MAX_PLANES 16
+typedef struct clslam_store_pack_desc {
+    const float* plane[CLSLAM_STORE_MAX_PLANES];
+    int32_t offset[CLSLAM_STORE_MAX_PLANES]; /* bytes from the slot's start */
+    int32_t count[CLSLAM_STORE_MAX_PLANES];  /* 3 * h * w */
+    int32_t n_planes;
+} clslam_store_pack_desc;
+typedef struct clslam_store_gather_desc {
+    float* rgb[CLSLAM_STORE_MAX_PLANES];
+    float* aug[CLSLAM_STORE_MAX_PLANES];
+    int64_t stride[CLSLAM_STORE_MAX_PLANES];
+    int32_t offset[CLSLAM_STORE_MAX_PLANES];
+    int32_t h[CLSLAM_STORE_MAX_PLANES], w[CLSLAM_STORE_MAX_PLANES]; /* by level */
+    int32_t n_frames, n_levels, capacity;                          /* capacity: slots in the store */
+    int64_t slot_bytes;
+} clslam_store_gather_desc;
+int clslam_store_pack(const clslam_store_pack_desc* desc, unsigned char* slot, unsigned long long* inexact, void* stream);
+int clslam_store_gather_jitter(const clslam_store_gather_desc* desc, const unsigned char* store, const int* slot_idx,
+                               const void* params, float* partial, int n_images, int row0, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loop-closure feature encoder: MobileNetV3-small forward (loop_closure_detection/encoder.py:13-33:

@@ -5,8 +5,11 @@ colour jitter, per sample and frame) + concatenation with the online sample + ad
 (slam.py:181-188), with the replay samples built
   (a) the reference's way: on the host with Pillow + torch CPU ops, then uploaded inside adapt(), and
   (b) by clslam_hip.ingest.ReplaySampleBuilder: PNG decode on the host (optionally cached), one uint8 upload, pyramid + jitter
-      on the GPU, concatenation on the GPU.
-    python tools/real_frame.py [frames=40] [K=4]
+      on the GPU, concatenation on the GPU, and
+  (c) by the same builder with a frame store (store_bytes > 0, no host cache): every sample was added from the pyramid the online
+      path holds at `add` time, `get` is two launches over bytes in HBM, cat_dict fills row 0.  Reported warm (steady state) and
+      for the first frames after a restart (store empty: every sample is a miss, decoded and packed).
+    python tools/real_frame.py [frames=40] [K=4] [modes: comma-separated substrings, default all]
 KITTI-sized PNGs (376x1241) are written to a temporary directory first.  Measurement tool (no parity claim: the parity of (b)
 is tests/test_replay_ingest.py); the host-side jitter in (a) is a plain torch restatement good enough for timing."""
 import pickle
@@ -27,6 +30,7 @@ from clslam_hip import ingest, synth  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+ONLY = sys.argv[3].split(',') if len(sys.argv) > 3 else None
 H, W, RAW_H, RAW_W, STORE = 192, 640, 376, 1241, 12
 FRAMES, SCALES = (0, -1, 1), (0, 1, 2, 3)
 work = Path(tempfile.mkdtemp())
@@ -101,6 +105,21 @@ online_host = {k: v.pin_memory() for k, v in synth.make_batch(1, H, W, seed=3).i
 builders = {'gpu ingest, PNGs decoded in one thread': ingest.ReplaySampleBuilder(H, W, SCALES, FRAMES, dev, decode_threads=1),
             'gpu ingest': ingest.ReplaySampleBuilder(H, W, SCALES, FRAMES, dev),            # 16 decode threads (default)
             'gpu ingest, decoded frames cached': ingest.ReplaySampleBuilder(H, W, SCALES, FRAMES, dev, cache_frames=3 * STORE)}
+STORE_MODE = 'gpu ingest, frame store'
+STORE_BYTES = STORE * ingest.FrameStore(H, W, SCALES, FRAMES, device=dev).slot_bytes
+
+
+def store_builder(fill):
+    b = ingest.ReplaySampleBuilder(H, W, SCALES, FRAMES, dev, store_bytes=STORE_BYTES)
+    if fill:            # what replay_buffer.add sees: the online sample's own pyramid, host tensors
+        for fn in files:
+            data = builders['gpu ingest'].get_many([fn])[0]
+            b.store.add_sample(fn, {k: v.cpu() for k, v in data.items() if k[0] == 'rgb'})
+        assert b.store.inexact_pixels() == 0 and len(b.store) == STORE
+    return b
+
+
+builders[STORE_MODE] = store_builder(fill=True)
 pick = np.random.default_rng(1)
 
 
@@ -121,8 +140,11 @@ def frame(mode, detail=False):
         t1 = time.perf_counter()
         training = {k: torch.cat([online[k], replay[k]]) for k in online if k in replay}              # slam.py:300-309
     else:
-        datas = builders[mode].get_many(fns)
-        replay = {k: torch.cat([d[k] for d in datas]) for k in datas[0]}
+        if builders[mode].store is not None:
+            replay = builders[mode].get_batch(fns)
+        else:
+            datas = builders[mode].get_many(fns)
+            replay = {k: torch.cat([d[k] for d in datas]) for k in datas[0]}
         t1 = time.perf_counter()
         training = ingest.cat_dict(online, replay, dev)
     sync()
@@ -140,7 +162,10 @@ def frame(mode, detail=False):
 
 
 print(f'real frame @{H}x{W}, K = {K} replay samples from a store of {STORE} ({RAW_H}x{RAW_W} PNGs), {N} frames per mode')
-for mode in ('reference get (host)', 'gpu ingest, PNGs decoded in one thread', 'gpu ingest', 'gpu ingest, decoded frames cached'):
+for mode in ('reference get (host)', 'gpu ingest, PNGs decoded in one thread', 'gpu ingest', 'gpu ingest, decoded frames cached',
+             STORE_MODE):
+    if ONLY is not None and not any(o in mode for o in ONLY):
+        continue
     random.seed(0)
     for _ in range(3 if mode == 'reference get (host)' else STORE):        # warm-up (and fill the decoded-frame cache)
         frame(mode)
@@ -158,3 +183,22 @@ for mode in ('reference get (host)', 'gpu ingest, PNGs decoded in one thread', '
         for _ in range(10):
             frame(mode, detail=True)
         print('      stage by stage, a synchronize between the stages (ms):', {k: round(v / 10 * 1e3, 2) for k, v in DETAIL.items()})
+
+if ONLY is None or any(o in STORE_MODE for o in ONLY):
+    # first sight after a restart: the store is empty, every one of the K samples is decoded, built by the PNG path and packed.
+    # One builder; its first frame (tap plans, decode pool, the store's allocation: once per process) is not counted.
+    first = 'first sight after restart'
+    builders[first] = store_builder(fill=False)
+    frame(first)
+    tf = tg = 0.0
+    for _ in range(5):
+        for fn in files:
+            builders[first].store.drop(fn)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tg += frame(first)
+        torch.cuda.synchronize()
+        tf += time.perf_counter() - t0
+    builders[first].close()
+    print(f'  {STORE_MODE + ", " + first:36s}: {tf / 5 * 1e3:8.2f} ms per frame  (5 frames, each on an empty store)   of which `get`: '
+          f'{tg / 5 * 1e3:7.2f} ms')
