@@ -963,6 +963,13 @@ __device__ __forceinline__ float si_edge_weight(const float* __restrict__ img, i
     return expf(-(g / 3.f));
 }
 
+// dz += v as an addition of its own: hipcc otherwise fuses the last product of v into it (v_fmac), and what is stored then
+// is not fl(dz + fl(v)).  Unfused, the kernel adds to any dz exactly what it writes into dz = 0 (tests/test_loss_kernels.py).
+__device__ __forceinline__ void si_accumulate(float* __restrict__ o, float v) {
+#pragma clang fp contract(off)
+    *o += v;
+}
+
 struct SiPtrs { const float* rgb0[4]; };
 struct SiDz { float* dz[4]; };
 
@@ -1035,7 +1042,7 @@ __global__ __launch_bounds__(256) void smooth_intended_bwd_kernel(Pyramid pyr, S
     if (y >= 1) g -= sgn(d[p - w] - dp) * si_edge_weight(img, hw, p - w, p) * ny;
     const float coef = smooth_scale / (float)(1 << sc) / 4.f * sample_w[b];
     const float dl = coef * (inv * g - T * inv * inv / (float)hw);
-    out.dz[sc][(size_t)b * hw + p] += dp * (1.f - dp) * dl;      // through the sigmoid of the disparity head
+    si_accumulate(out.dz[sc] + (size_t)b * hw + p, dp * (1.f - dp) * dl);      // through the sigmoid of the disparity head
 }
 
 }  // namespace clslam
@@ -1064,7 +1071,7 @@ extern "C" int clslam_smooth_intended_finalize(const float* partial, const float
 
 extern "C" int clslam_smooth_intended_bwd(const float* const* disp, const float* const* rgb0, const float* aux, const float* sample_w,
                                           float* const* dz, int batch, int H, int W, float smooth_scale, void* stream) {
-    CLSLAM_REQUIRE(disp && rgb0 && aux && sample_w && dz, "smooth_intended_bwd: null");
+    CLSLAM_REQUIRE(disp && rgb0 && aux && sample_w && dz && (H >> 3) >= 2 && (W >> 3) >= 2, "smooth_intended_bwd: bad args");
     if (!batch) return CLSLAM_OK;
     clslam::SiPtrs im;
     clslam::SiDz out;

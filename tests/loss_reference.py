@@ -11,6 +11,8 @@ networks/layers.py:51-137, dpp.py:986-1192; oracle/functional.py is called where
     photo_backward / warp_backward       dL / d warped, dL / d upsampled disparity and dL / dP by autograd
     disp_backward                        dL / d disparity logit
     pose_backward                        dL / d pose-decoder output
+    smooth_intended_T / _finalize /      the opt-in per-sample smoothness: its chunked sums, what its finalize does to
+      _backward                          the 18 loss scalars, and dL / d disparity logit
 
 Everything is loop-free torch evaluated in `dtype`: float64 is the reference, float32 the yardstick ("what the same
 formula loses in the kernel's own number format").  Gradients come from autograd through the restatement -- no analytic
@@ -283,3 +285,57 @@ def pose_backward(dp_partial, pose, K, dist0, dist1, sample_w, vel_scale, dtype=
         L = L + (vel_scale * OF.velocity_loss(p[:B, 3:6], p[B:2 * B, 3:6], dist0, dist1).to(dtype) * sample_w.to(dtype)).sum()
     g, = torch.autograd.grad(L, p)
     return g
+
+
+# ---- the per-sample ("intended") smoothness -----------------------------------------------------------------------------
+def smooth_intended_T(disp_s, rgb0_s, dtype=F64, chunks=32):
+    """what smooth_intended_fwd_kernel sums for one scale: disp_s (B,h,w) raw disparity, rgb0_s (B,3,h,w) ->
+    T (B,) = mean_{y, x<w-1} |d(y,x) - d(y,x+1)| exp(-mean_c |I(y,x) - I(y,x+1)|) + the same along y
+    (oracle.functional.smooth_loss_intended of the un-normalised disparity), and the same quantity cut into `chunks` ranges
+    of ceil(h w / chunks) consecutive pixels (B,chunks): the edge to the right of and the edge below pixel p both belong to
+    p; a range past the last pixel is empty."""
+    d, img = disp_s.to(dtype), rgb0_s.to(dtype)
+    B, h, w = d.shape
+    T = OF.smooth_loss_intended(d[:, None], img)
+    per_px = torch.zeros(B, h, w, dtype=dtype)
+    per_px[:, :, :-1] += (d[:, :, :-1] - d[:, :, 1:]).abs() * torch.exp(-(img[:, :, :, :-1] - img[:, :, :, 1:]).abs().mean(1)) / (h * (w - 1))
+    per_px[:, :-1, :] += (d[:, :-1, :] - d[:, 1:, :]).abs() * torch.exp(-(img[:, :, :-1, :] - img[:, :, 1:, :]).abs().mean(1)) / ((h - 1) * w)
+    per = -(-h * w // chunks)
+    return T, F.pad(per_px.reshape(B, h * w), (0, per * chunks - h * w)).reshape(B, chunks, per).sum(2)
+
+
+def smooth_intended_finalize(partial, means, sample_w, losses, H, W, smooth_scale, dtype=F64):
+    """what smooth_intended_finalize_kernel writes: partial (4,B,chunks) chunk sums of T, means (4,B,chunks') chunk sums of
+    the disparity, losses (18) as they were before -> aux (4,B,2) = (1 / (mean_b + 1e-7), T_b), the 18 losses after
+    (sm_s = sum_b inv_b T_b sample_w[b] into 4s+1, reg_s = smooth_scale / 2^s * sm_s into 4s+2, reg_s added to 4s+3,
+    sum_s reg_s / 4 added to 17, the rest as it was) and reg (4,)."""
+    sw, out = sample_w.to(dtype), losses.to(dtype).clone()
+    aux, regs = [], []
+    for s in range(4):
+        inv = 1 / (means[s].to(dtype).sum(1) / ((H >> s) * (W >> s)) + 1e-7)
+        T = partial[s].to(dtype).sum(1)
+        sm = (inv * T * sw).sum()
+        reg = smooth_scale / 2 ** s * sm
+        out[4 * s + 1], out[4 * s + 2], out[4 * s + 3] = sm, reg, out[4 * s + 3] + reg
+        aux.append(torch.stack([inv, T], 1))
+        regs.append(reg)
+    regs = torch.stack(regs)
+    out[17] = out[17] + regs.sum() / 4
+    return torch.stack(aux), out, regs
+
+
+def smooth_intended_backward(disps, rgb0s, sample_w, smooth_scale, dtype=F64):
+    """dL / dz per scale [(B,h,w)] by autograd, disp = sigmoid(z),
+    L = sum_s smooth_scale / 2^s / 4 * sum_b sample_w[b] * smooth_loss_intended(disp_s / (mean(disp_s) + 1e-7), rgb0_s)[b].
+    The forward VALUE of disp is the given tensor to the bit (sigmoid(logit(d)) would move it by a rounding, and with it
+    the sign of a difference of two almost equal neighbours); only the derivative runs through the sigmoid."""
+    zs, L = [], 0
+    for s in range(4):
+        d = disps[s].to(dtype)
+        z = torch.log(d / (1 - d)).requires_grad_(True)
+        sg = torch.sigmoid(z)
+        disp = d + (sg - sg.detach())
+        n = disp / (disp.mean((1, 2), keepdim=True) + 1e-7)
+        L = L + smooth_scale / 2 ** s / 4 * (OF.smooth_loss_intended(n[:, None], rgb0s[s].to(dtype)) * sample_w.to(dtype)).sum()
+        zs.append(z)
+    return list(torch.autograd.grad(L, zs))

@@ -47,6 +47,13 @@ the worst case over all cases and scales of each quantity (every row is printed 
   disp_grad dz max                             1.97e-09 | 1.74e-09 (1.13x)     5.50e-10 | 4.34e-10 (1.27x)
   disp_grad_pyramid dz max                     2.91e-10 | 3.82e-10 (0.76x)     2.91e-10 | 3.82e-10 (0.76x)
   pose_bwd dpose max (|ref| 2.5e+04)           4.88e-04 | 1.38e-01 (0.004x)    4.88e-04 | 1.38e-01 (0.004x)
+  smooth_intended_fwd chunk sums, relative     1.69e-07 | 1.17e-07 (bound 1.3e-06)   1.91e-07 | 1.17e-07 (bound 1.3e-06)
+  smooth_intended_fwd T, relative              5.52e-08 | 2.15e-08 (bound 1.3e-06)   4.90e-08 | 2.15e-08 (bound 1.3e-06)
+  smooth_intended_finalize aux max rel         2.90e-07 | 1.45e-07 (bound 2.1e-06)   the same
+  smooth_intended_finalize losses max rel      2.88e-07 | 1.66e-07 (bound 4.4e-06)   3.58e-07 | 2.48e-07 (bound 4.4e-06)
+  smooth_intended_bwd dz max (|ref| 4.8e-04)   1.14e-10 | 8.47e-11 (1.35x)     6.34e-11 | 8.47e-11 (0.75x)
+  smooth_intended_bwd dz rel L2                1.88e-07 | 1.64e-07 (1.15x)     1.45e-07 | 1.11e-07 (1.31x)
+  (the largest ratio of any smooth_intended_bwd row, any case, scale and smooth_scale: 1.35x emu, 1.31x hip)
 photo_grad: before photo_grad_px summed alpha + beta x + gamma y per neighbour (csrc/loss.hip) the emulator gave
 photo_grad dpred 3.45e-09 | 3.87e-10 (8.9x): the check that failed.
 
@@ -64,6 +71,28 @@ test_loss_stage.py (as it was), test_backward_parity.py and test_warp_positions.
   dPs[fi * 12 + k] -> dPs[k]                               test_pose_bwd[0.05-random-4-8]                before: yes
   `raw.x <= 1.f` dropped from kf (photo_automask)          SURVIVES, equivalent: |S| <= 1 (see _photo_pair), raw > 1 cannot occur;
       dropping `raw.x >= 0.f` survives too: raw < 0 arises only by rounding at S = 1, where the coefficients vanish anyway
+
+The three smooth_intended_* kernels, same procedure; "before" = whether test_smooth_intended.py as it was (one case: 64 x 64,
+B = 2, uniform weights, gradients at 3e-2) caught it on the emulator.  Each test named fails at every case but those in ():
+  nx / ny swapped in smooth_intended_fwd_kernel            test_smooth_intended_fwd[32x96-B3]  (16x16: nx == ny)  before: no
+  nx / ny swapped in smooth_intended_bwd_kernel            test_smooth_intended_bwd[32x96-B3]  (16x16)            before: no
+  sample_w[0] for sample_w[b] in the backward              test_smooth_intended_bwd[32x96-B3]  (16x16: B = 1)     before: no
+  sample_w[0] for sample_w[b] in the finalize              test_smooth_intended_finalize[arbitrary-32x96-B3] (16x16)  before: no
+  `- T * inv * inv / hw` dropped                           test_smooth_intended_bwd[32x96-B3]                     before: yes
+  `/ (float)(1 << sc)` dropped in the backward             test_smooth_intended_bwd[32x96-B3]                     before: yes
+  si_edge_weight(img, hw, p - 1, p) -> (p, p + 1)          test_smooth_intended_bwd[32x96-B3]                     before: no
+  `+=` -> `=` on the dz store                              test_smooth_intended_bwd[32x96-B3]                     before: yes
+  `/ 4.f` dropped from the losses[17] update               test_smooth_intended_finalize[arbitrary-32x96-B3]      before: yes
+  `y + 1 <= h` in the forward (an edge past the sample)    test_smooth_intended_fwd[32x96-B3]                     before: yes
+      (the next sample's first row changes the value; behind the last sample the NaN around the inputs shows it)
+  y = p / h for p / w in the backward / in the forward     test_smooth_intended_bwd / _fwd[32x96-B3]  (16x16)     before: no / no
+Of the engine-level tests test_smooth_intended.py has now, the 64 x 128 oracle case fails for the forward nx / ny swap and
+the two p / h ones but not for the backward nx / ny swap or the edge-weight one (they stay inside its 3e-2);
+test_intended_smoothness_gradient_alone fails for all five.  Neither sees sample_w[0] (the engine's weights are uniform).
+None survives.
+The backward's store: hipcc fused the last product of the gradient into `dz +=` (v_fmac_f32), so on gfx950 the kernel wrote
+fl(dz + a * dl) with a * dl unrounded, and dz was not fl32(what was there + what a run on zeros writes); the emulator (no
+contraction) could not show it, the gfx950 assembly did.  si_accumulate() in csrc/loss.hip keeps the addition unfused.
 """
 import math
 
@@ -73,6 +102,7 @@ import torch
 
 import loss_reference as R
 from clslam_hip import ops, synth
+from clslam_hip._lib import ClslamError
 from emu_util import BACKENDS, use_backend
 
 U = 2.0 ** -24          # unit round-off of fp32
@@ -848,3 +878,227 @@ def test_pose_bwd(backend, nscale, nblk, partials, vel_scale, capsys):
         ek = float((dpose[n, :6].cpu().double() - r64[n, :6]).abs().max())
         assert ek <= 4 * e32 + 2 * U * float(r64[n, :6].abs().max()), (n, ek, e32)     # + the final rounding of the output to fp32
     _flush(capsys)
+
+
+# ---- the opt-in per-sample ("intended") smoothness: smooth_intended_fwd / _finalize / _bwd --------------------------------
+# B, H, W, sample_w: non-square with three samples; scale 3 = 3x20; scale 3 = 2x2, the smallest the entry points accept (4 pixels
+# in 32 chunks); 320 pixels per chunk at scale 0 (the 256-thread stride loop wraps)
+SI_CASES = [
+    pytest.param(3, 32, 96, (0.1, 0.6, 0.3), id='32x96-B3'), pytest.param(2, 24, 160, (0.8, 0.2), id='24x160-B2'),
+    pytest.param(1, 16, 16, (0.7,), id='16x16-B1'), pytest.param(2, 64, 160, (0.8, 0.2), id='64x160-B2')]
+SI_SCALES = (1e-3, 0.1)          # smooth_scale: the shipped weight and the one test_smooth_intended.py uses
+GUARD = 7.0
+
+
+def _guarded(t, dev, guard, fill=NAN):
+    """t on `dev` as a view into a buffer that holds `guard` elements of `fill` before and behind it -> (buffer, view)"""
+    n = t.numel()
+    buf = torch.full((n + 2 * guard,), fill, dtype=t.dtype)
+    buf[guard:guard + n] = t.reshape(-1)
+    buf = buf.to(dev)
+    return buf, buf[guard:guard + n].view(t.shape)
+
+
+def _guards_intact(buf, guard, fill=GUARD):
+    return bool((buf[:guard] == fill).all()) and bool((buf[-guard:] == fill).all())
+
+
+def _si_inputs(seed, B, H, W):
+    """disparities and target images of the four scales.  Every sample holds a block of EXACTLY equal disparities (2 x 3; at
+    2 x 2 three of the four pixels), i.e. differences of 0 along x and along y: sgn(0) = 0 of the backward has to meet the
+    abs'(0) = 0 of autograd, and the forward adds nothing there."""
+    g = _gen(seed)
+    disps = _disps(g, B, H, W, 0.05, 0.95)
+    rgb0 = [_images(g, B, h, w)[1] for h, w in _pyramid_shapes(H, W)]
+    for d in disps:
+        h, w = d.shape[-2:]
+        for b in range(B):
+            if w >= 4:
+                d[b, h // 2 - 1:h // 2 + 1, 1:4] = 0.3 + 0.125 * b
+            else:
+                d[b, 0, :] = d[b, 1, 0] = 0.3 + 0.125 * b
+        assert bool((d[:, :, :-1] == d[:, :, 1:]).any(2).any(1).all()) and bool((d[:, :-1] == d[:, 1:]).any(2).any(1).all())
+        assert float((d[:, :, :-1] != d[:, :, 1:]).double().mean()) >= 0.5
+    return disps, rgb0
+
+
+def _si_device_inputs(disps, rgb0, dev, W):
+    """views whose surroundings are NaN: an edge taken past the first or last pixel of the batch turns the result into NaN
+    (an edge taken into the NEXT sample changes the value instead)"""
+    return [_guarded(d, dev, W)[1] for d in disps], [_guarded(i, dev, W)[1] for i in rgb0]
+
+
+def _chunk_sums(t, chunks):
+    """(B, ...) -> (B, chunks) float64 sums over ranges of ceil(n / chunks) consecutive elements"""
+    B, n = t.shape[0], t[0].numel()
+    per = -(-n // chunks)
+    return torch.nn.functional.pad(t.double().reshape(B, n), (0, per * chunks - n)).reshape(B, chunks, per).sum(2)
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+@pytest.mark.parametrize('B,H,W,sw', SI_CASES)
+def test_smooth_intended_fwd(backend, B, H, W, sw, capsys):
+    """The 4 x B x 32 chunk sums against float64, chunk by chunk, and their float64 sum against T (stated twice in the
+    reference: by oracle.functional.smooth_loss_intended and as the sum of the chunks).  Derived bound: a chunk is a sum of
+    non-negative terms |d_p - d_q| e nx; a term carries k = 12 roundings (the difference 1; the argument of expf is a sum of
+    three |differences| / 3 <= 1: 3 + 2 + 1 roundings of a number <= 1 move e by <= 4 u relative after the exponential,
+    expf itself at 2 ulp = 4 u; two products; nx), a thread adds 2 cdiv(per, 256) of them, the block 6 shuffle levels and 2
+    adds: (2 cdiv(per, 256) + 8 + 12) u relative.  Chunks past the last pixel (16x16: 28 of 32 at level 3, 16 at level 2)
+    are exactly 0, as are chunks of tied pixels only.  `partial` lies between guard elements; it is pre-filled with NaN, so
+    every chunk is written.  The fp32 restatement's figure is printed beside the kernel's."""
+    dev = use_backend(backend)
+    name = f'smooth_intended_fwd {H}x{W}'
+    disps, rgb0 = _si_inputs(81, B, H, W)
+    chunks = ops.smooth_intended_chunks()
+    assert chunks == 32
+    refs = [(R.smooth_intended_T(disps[s], rgb0[s], F64, chunks), R.smooth_intended_T(disps[s], rgb0[s], F32, chunks)) for s in range(4)]
+    disps_d, rgb0_d = _si_device_inputs(disps, rgb0, dev, W)
+    buf, partial = _guarded(torch.full((4, B, chunks), NAN), dev, 64, GUARD)
+    ops.smooth_intended_fwd(disps_d, rgb0_d, partial, H, W)
+    assert _guards_intact(buf, 64)
+    got = partial.cpu().double()
+    assert torch.isfinite(got).all()
+    for s, (h, w) in enumerate(_pyramid_shapes(H, W)):
+        (T64, c64), (T32, c32) = refs[s]
+        per = -(-h * w // chunks)
+        n = 2 * -(-per // 256) + 8 + 12
+        assert float(((c64.sum(1) - T64).abs() / T64).max()) < 1e-13 and bool((T64 > 0).all())
+        empty = torch.arange(chunks) * per >= h * w
+        assert bool((got[s][:, empty] == 0).all()) and bool((got[s][c64 == 0] == 0).all())
+        rel = lambda v, r: float(((v - r).abs() / r.clamp_min(1e-300)).max())
+        _row(backend, name + f' s{s}', 'chunks max rel', rel(got[s], c64), rel(c32.double(), c64), f'(bound {n} u = {n * U:.1e}, {int(empty.sum())} empty)')
+        _row(backend, name + f' s{s}', 'T max rel', rel(got[s].sum(1), T64), rel(T32.double(), T64))
+        assert bool(((got[s] - c64).abs() <= n * U * c64).all()), (s, rel(got[s], c64))
+        assert bool(((got[s].sum(1) - T64).abs() <= n * U * T64).all()), s
+    if (H, W) == (64, 160):
+        assert -(-H * W // chunks) > 256                    # the block's stride loop wraps at level 0
+    _flush(capsys)
+
+
+def _si_finalize_inputs(B, H, W):
+    """partial and the disparity chunk sums as INPUTS: the float64 sums rounded to fp32"""
+    disps, rgb0 = _si_inputs(82, B, H, W)
+    partial = torch.stack([R.smooth_intended_T(disps[s], rgb0[s], F64, ops.smooth_intended_chunks())[1] for s in range(4)]).float()
+    means = torch.stack([_chunk_sums(disps[s], ops.disp_mean_chunks()) for s in range(4)]).float()
+    return disps, rgb0, partial.contiguous(), means.contiguous()
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+@pytest.mark.parametrize('B,H,W,sw', SI_CASES)
+@pytest.mark.parametrize('prefill', ['arbitrary', 'loss_finalize'])
+def test_smooth_intended_finalize(backend, B, H, W, sw, prefill, capsys):
+    """aux and the 18 losses at both smooth_scale values, on chunk sums the test rounds from float64.  `losses` holds 18
+    positive numbers before ('arbitrary': drawn; 'loss_finalize': what ops.loss_finalize(..., n_smooth=0) wrote on inputs of
+    its own -- the engine's sequence).  Entries 4s and 16 keep their bits; 4s + 1 and 4s + 2 are overwritten by sm_s, reg_s;
+    4s + 3 grows by reg_s and 17 by sum_s reg_s / 4; losses and aux lie between guard elements.
+    Derived bounds (sums of non-negative terms, u per rounding): inv_b = 1 / (sum of dm chunk sums / hw + 1e-7): (dm + 3) u;
+    T_b: 32 u; sm_s sums B products inv T w: (dm + 3 + 32 + 2 + B) u = n u; reg_s: + 2 (smooth_scale as fp32, the product;
+    2^-s is exact); 4s + 3: the rounding of the sum, u |result|, + the error of reg_s; 17: the four reg_s added (+ 4, / 4
+    exact), then as for 4s + 3.  The fp32 restatement's figure is printed beside the kernel's."""
+    dev = use_backend(backend)
+    disps, rgb0, partial, means = _si_finalize_inputs(B, H, W)
+    swt = torch.tensor(sw)
+    dm = ops.disp_mean_chunks()
+    g = _gen(83)
+    for smooth_scale in SI_SCALES:
+        if prefill == 'arbitrary':
+            before = 0.2 + torch.rand(18, generator=g)
+        else:
+            nblk = ops.automask_blocks(H, W)
+            parts = [(0.03 + 0.05 * torch.rand(B, nblk, generator=g)) * 512 for _ in range(4)]
+            pose = torch.randn(2 * B, 12, generator=g) * 0.1
+            dist0, dist1 = (0.3 + torch.rand(B, dtype=F64, generator=g) for _ in range(2))
+            lf = torch.full((18,), NAN, device=dev)
+            ops.loss_finalize(_dev_list(parts, dev), _dev_list(disps, dev), _dev_list(rgb0, dev), _dev_list(list(means), dev), pose.to(dev),
+                              dist0.to(dev), dist1.to(dev), swt.to(dev), None, lf, None, B, nblk, H, W, 0, smooth_scale, 0.05)
+            before = lf.cpu()
+            assert bool((before[[0, 3, 4, 7, 8, 11, 12, 15, 16, 17]] > 0).all()) and bool((before[[1, 2, 5, 6, 9, 10, 13, 14]] == 0).all())
+        A64, L64, reg64 = R.smooth_intended_finalize(partial, means, swt, before, H, W, smooth_scale)
+        A32, L32, _ = R.smooth_intended_finalize(partial, means, swt, before, H, W, smooth_scale, F32)
+        lbuf, losses = _guarded(before, dev, 8, GUARD)
+        abuf, aux = _guarded(torch.full((4, B, 2), NAN), dev, 8, GUARD)
+        ops.smooth_intended_finalize(partial.to(dev), means.to(dev), swt.to(dev), losses, aux, B, H, W, smooth_scale)
+        assert _guards_intact(lbuf, 8) and _guards_intact(abuf, 8)
+        got, ga = losses.cpu(), aux.cpu().double()
+        keep = [0, 4, 8, 12, 16]
+        assert torch.equal(got[keep], before[keep])
+        got = got.double()
+        n = dm + 37 + B
+        tol_a = torch.stack([(dm + 3) * U * A64[..., 0], 32 * U * A64[..., 1]], -1)
+        tol = torch.zeros(18, dtype=F64)
+        for s in range(4):
+            tol[4 * s + 1], tol[4 * s + 2] = n * U * L64[4 * s + 1], (n + 2) * U * L64[4 * s + 2]
+            tol[4 * s + 3] = U * L64[4 * s + 3] + (n + 2) * U * reg64[s]
+        tol[17] = U * L64[17] + (n + 6) * U * reg64.sum() / 4
+        assert bool((reg64 > 0).all()) and bool((L64[[3, 7, 11, 15, 17]] > before.double()[[3, 7, 11, 15, 17]]).all())
+        rel = lambda v, r: float(((v - r).abs() / r.abs().clamp_min(1e-300)).max())
+        name = f'smooth_intended_finalize {H}x{W} {prefill} {smooth_scale:g}'
+        _row(backend, name, 'aux max rel', rel(ga, A64), rel(A32.double(), A64), f'(bound {dm + 3} u = {(dm + 3) * U:.1e})')
+        _row(backend, name, 'losses max rel', rel(got, L64), rel(L32.double(), L64), f'(bound {n + 2} u = {(n + 2) * U:.1e})')
+        assert bool(((ga - A64).abs() <= tol_a).all()), ((ga - A64).abs() / tol_a).max()
+        assert bool(((got - L64).abs() <= tol).all()), ((got - L64).abs() / tol.clamp_min(1e-300)).tolist()
+    _flush(capsys)
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+@pytest.mark.parametrize('B,H,W,sw', SI_CASES)
+def test_smooth_intended_bwd(backend, B, H, W, sw, capsys):
+    """dz of smooth_intended_bwd at both smooth_scale values against float64 autograd of the weighted, mean-normalised
+    smoothness of the four scales through disp = sigmoid(z): measured class, 4 x the fp32 restatement per scale (largest
+    absolute error and relative L2), every pixel included -- the sign of an fp32 difference is the sign of the exact one, and
+    on the tied block both sides give 0.  aux = (1 / (mean + 1e-7), T) is the float64 reference's, rounded to fp32.
+    The kernel ADDS: on a dz that holds numbers of the gradient's own size it writes fl32(what was there + what it writes
+    on zeros), bit for bit.  The four dz are views between guard elements (the launch has cdiv(H W, 256) blocks for every
+    scale: at scale 3 all but one are past the last pixel)."""
+    dev = use_backend(backend)
+    disps, rgb0 = _si_inputs(84, B, H, W)
+    swt = torch.tensor(sw)
+    disps_d, rgb0_d = _si_device_inputs(disps, rgb0, dev, W)
+    aux = torch.stack([torch.stack([1 / (disps[s].double().mean((1, 2)) + 1e-7), R.smooth_intended_T(disps[s], rgb0[s])[0]], 1)
+                       for s in range(4)]).float().contiguous()
+    g = _gen(85)
+    for smooth_scale in SI_SCALES:
+        r64 = R.smooth_intended_backward(disps, rgb0, swt, smooth_scale)
+        r32 = R.smooth_intended_backward(disps, rgb0, swt, smooth_scale, F32)
+        runs = []
+        for fill in (False, True):
+            pre = [torch.randn(d.shape, generator=g) * float(r64[s].abs().max()) if fill else torch.zeros(d.shape) for s, d in enumerate(disps)]
+            bufs, dzs = zip(*[_guarded(p, dev, 256, GUARD) for p in pre])
+            ops.smooth_intended_bwd(disps_d, rgb0_d, aux.to(dev), swt.to(dev), list(dzs), H, W, smooth_scale)
+            assert all(_guards_intact(b, 256) for b in bufs)
+            runs.append((pre, [d.cpu() for d in dzs]))
+        for s in range(4):
+            name = f'smooth_intended_bwd {H}x{W} s{s} {smooth_scale:g}'
+            tied = (disps[s][:, :, :-1] == disps[s][:, :, 1:])
+            assert float(r64[s].abs().max()) > 0 and bool(tied.any())
+            _measured(backend, name, 'dz', runs[0][1][s], r64[s], r32[s])
+            assert torch.equal(runs[1][1][s], runs[1][0][s] + runs[0][1][s]), (s, 'dz is not what was there + the gradient')
+            assert not torch.equal(runs[1][1][s], runs[0][1][s])
+    _flush(capsys)
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+def test_smooth_intended_geometry(backend):
+    """H = 8 or W = 8 (a scale-3 map of one row or one column: no edge along y / x, ny or nx = 1 / 0) is rejected by the
+    forward AND by the backward, before anything is written; B = 0 returns without touching anything."""
+    dev = use_backend(backend)
+    chunks = ops.smooth_intended_chunks()
+    one = torch.ones(1, device=dev)
+    for B, H, W in ((2, 8, 32), (2, 32, 8), (0, 32, 96)):
+        disps = [torch.rand(max(B, 1), h, w)[:B].contiguous().to(dev) for h, w in _pyramid_shapes(H, W)]
+        rgb0 = [torch.rand(max(B, 1), 3, h, w)[:B].contiguous().to(dev) for h, w in _pyramid_shapes(H, W)]
+        partial = torch.full((4, max(B, 1), chunks), GUARD, device=dev)
+        aux = torch.full((4, max(B, 1), 2), 0.5, device=dev)
+        dzs = [torch.full((max(B, 1), h, w), GUARD, device=dev) for h, w in _pyramid_shapes(H, W)]
+        losses = torch.full((18,), GUARD, device=dev)
+        if B:
+            with pytest.raises(ClslamError):
+                ops.smooth_intended_fwd(disps, rgb0, partial, H, W)
+            with pytest.raises(ClslamError):
+                ops.smooth_intended_bwd(disps, rgb0, aux, one, dzs, H, W, 0.1)
+        else:
+            ops.smooth_intended_fwd(disps, rgb0, partial, H, W)
+            ops.smooth_intended_finalize(partial, partial, one, losses, aux, B, H, W, 0.1)
+            ops.smooth_intended_bwd(disps, rgb0, aux, one, dzs, H, W, 0.1)
+        assert bool((partial == GUARD).all()) and bool((losses == GUARD).all()) and bool((aux == 0.5).all())
+        assert all(bool((d == GUARD).all()) for d in dzs)
