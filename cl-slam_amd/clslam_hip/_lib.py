@@ -36,10 +36,6 @@ class TransposeItem(C.Structure):
     _fields_ = [('w', fptr), ('wt', fptr), ('ch_out', i32), ('taps', i32), ('ch_in', i32), ('ch_in_sel', i32)]
 
 
-class CopyItem(C.Structure):
-    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('bytes', C.c_size_t)]
-
-
 class LossDesc(C.Structure):
     _fields_ = [('partial', fptr * 4), ('disp', fptr * 4), ('rgb0', fptr * 4), ('means', fptr * 4),
                 ('pose', fptr), ('dist0', fptr), ('dist1', fptr), ('sample_w', fptr), ('smooth_w', fptr),
@@ -80,7 +76,6 @@ _SIGNATURES = {
     'clslam_conv_wgrad_patch': [C.POINTER(ConvDesc), fptr, fptr, i32, C.c_void_p],
     'clslam_reduce_partials': [fptr, fptr, C.c_size_t, i32, C.c_float, C.c_void_p],
     'clslam_reduce_multi': [fptr, i32, i32, C.c_void_p],
-    'clslam_reduce_multi_adam': [fptr, i32, i32, fptr, fptr, fptr, fptr, C.c_double, C.c_double, C.c_double, C.c_double, i32, fptr, C.c_void_p],
     'clslam_colsum_blocks': [i32],
     'clslam_colsum': [fptr, fptr, i32, i32, C.c_void_p],
     'clslam_stem_packed_size': [i32],
@@ -141,7 +136,6 @@ _SIGNATURES = {
     'clslam_adam_step': [fptr, fptr, fptr, fptr, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double, i32, C.c_float,
                          fptr, C.c_void_p],
     'clslam_disp_grad': [fptr, fptr, fptr, i32, fptr, i32, i32, i32, i32, i32, C.c_void_p],
-    'clslam_copy_multi': [C.c_void_p, i32, C.c_void_p],
     'clslam_handoff_arm': [C.c_void_p],
     'clslam_handoff_wait': [C.c_void_p, C.c_void_p, C.c_void_p],
     'clslam_conv_profile_begin': [i32],
@@ -168,7 +162,7 @@ _SIGNATURES = {
     'clslam_pcl_resolve': [fptr, fptr, C.c_longlong, fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
-ABI_VERSION = 108          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
+ABI_VERSION = 109          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32]}      # return size_t
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}

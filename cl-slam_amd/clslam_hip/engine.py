@@ -17,6 +17,7 @@ Reference call graph being replaced: dpp.py:906-923 (_process_batch), :925-974, 
 :1019-1120, and dpp.py:309-313 (zero_grad / backward / optimizer.step).
 """
 import contextlib
+import itertools
 import math
 import os
 from types import SimpleNamespace
@@ -100,13 +101,13 @@ _STREAM_POOL: Dict[Any, Dict[str, Any]] = {}
 
 
 def _device_streams(device) -> Dict[str, Any]:
-    """side / wgrad / capture / tail streams of this process on `device` (created once)."""
+    """main / side / wgrad / tail streams of this process on `device` (created once)."""
     if device.type != 'cuda':
         return {}
     key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
     pool = _STREAM_POOL.get(key)
     if pool is None:
-        pool = {name: torch.cuda.Stream(device=device, priority=0) for name in ('main', 'side', 'wg', 'tail', 'capture')}
+        pool = {name: torch.cuda.Stream(device=device, priority=0) for name in ('main', 'side', 'wg', 'tail')}
         _STREAM_POOL[key] = pool
     return pool
 
@@ -144,12 +145,10 @@ class Engine:
         self.adam_step_count = 0
         self.enc: Dict[str, Any] = {}
         self._ws: Dict[int, SimpleNamespace] = {}
-        self._graphs: Dict[Any, SimpleNamespace] = {}
         self.models = None
         self._packed_version = None
         self._tracked = None
         self._modules_stale = False
-        self.fresh_outputs = True
         # The streams are shared by every engine of the process on this device (HIP spreads a process's streams over four
         # hardware queues: 3.84 instead of 3.33 ms per step with three predictors' private streams).
         pool = _device_streams(device)
@@ -172,8 +171,7 @@ class Engine:
         self.wg_stream = pool.get('wg')
         # split-K scratch of the small-M 3x3 convs: one zero-filled buffer per stream convs are launched on
         self._conv_ws: Dict[int, torch.Tensor] = pool.setdefault('conv_ws', {}) if pool else {}
-        self.capture_stream = pool.get('capture')
-        for st in (self.main_stream, self.side_stream, self.wg_stream, self.capture_stream):
+        for st in (self.main_stream, self.side_stream, self.wg_stream):
             if st is not None:
                 self._conv_workspace(st.cuda_stream)
         # Asynchronous tail (data-parallel mode): gradient reduction + all-reduce + Adam of step N run on `tail_stream` and the
@@ -184,11 +182,6 @@ class Engine:
         self.tail_stream = pool.get('tail')
         self._tail_event = None       # optimizer step in flight on tail_stream
         self._tail_open = False       # backward() left its reduction on tail_stream; adam() closes it
-        # CLSLAM_FUSE_ADAM=1 (opt-in, single GPU): gradient reduction + optimizer step as ONE launch (clslam_reduce_multi_adam;
-        # backward(defer_reduce=True) leaves the reduction to adam()).  Bitwise the two launches (tests/test_adam.py), not faster:
-        # 3.316 vs 3.311 ms at B = 5, 1.515 vs 1.454 ms at K = 0 (DESIGN.md "Round 3").
-        self.fuse_adam = os.environ.get('CLSLAM_FUSE_ADAM', '0') == '1'
-        self._pending_reduce = None
         # Descriptor memo: slam.py:143-147 runs models['depth_encoder'](online_image) on every frame right
         # before adapt(), whose depth-encoder pass over the (un-augmented) online sample repeats it.  run_encoder() keeps its input
         # and features; a single-triplet forward whose network input has the same CONTENT takes them instead of 22 launches.
@@ -204,7 +197,6 @@ class Engine:
         self.time_exchange = False    # bench.py --gpus N: time the bucket all-reduces (exchange_report())
         self.exchange_events: List[Any] = []
         self.exchange_main_done = None
-        self._capturing = False
         # tie-break noise drawn in the loss kernel (Philox): keyed by the seed of torch's generator of this device, re-read on
         # every forward -- torch.manual_seed() after construction re-keys the stream and restarts its draw counter, like the
         # global generator the reference draws from (dpp.py:1055-1056).  noise_stream = the data-parallel shard offset: ranks
@@ -215,7 +207,7 @@ class Engine:
         self.noise_stream = 0
         # A side stream is released behind ONE launch of the dependency chain by that launch's own completion signal (+1.3 us on
         # the producer) instead of an event recorded behind it (+5.0 us, ~17 hand-offs per step: tools/micro/event_gap.hip,
-        # profiles/r05_micro_calibration.txt).  Graph capture and ops.PROFILE runs still record events.
+        # profiles/r05_micro_calibration.txt).  ops.PROFILE runs still record events.
         self._handoff = ops.Handoff() if device.type == 'cuda' else None
         self._cu_enc = self._cu_dec = self._cu_pose = self._cu_depth = 0     # cu_limit() per forward(); the stand-alone callables (run_encoder, ...) take the whole chip
         self.device_cus = (torch.cuda.get_device_properties(device).multi_processor_count if device.type == 'cuda' else 256)
@@ -249,15 +241,14 @@ class Engine:
             self.pack()
 
     def _on(self, st):
-        """context: the launches of the block go to stream `st`.  Outside graph capture this is ops.launch_on (no change of
-        torch's current stream, 0.3 us instead of 6): the blocks it wraps contain launches of clslam_hip.ops only."""
+        """context: the launches of the block go to stream `st`.  This is ops.launch_on (no change of torch's current stream,
+        0.3 us instead of 6): the blocks it wraps contain launches of clslam_hip.ops only."""
         if st is None:
             return contextlib.nullcontext()
-        return torch.cuda.stream(st) if self._capturing else ops.launch_on(st)
+        return ops.launch_on(st)
 
     def _use_tail(self) -> bool:
-        return (self.async_tail and self.tail_stream is not None and self.device.type == 'cuda' and not self._capturing
-                and ops.PROFILE is None)
+        return self.async_tail and self.tail_stream is not None and self.device.type == 'cuda' and ops.PROFILE is None
 
     def _side_streams(self):
         """(side, wg): the pose branch's and the wgrad stream; None each when use_side_stream is off or there is none"""
@@ -327,7 +318,7 @@ class Engine:
     def detached_ok(self) -> bool:
         """A training adapt() may run on the engine's own stream (see __init__)."""
         return (self.detached_training and self.main_stream is not None and self.device.type == 'cuda'
-                and not self._capturing and ops.PROFILE is None)
+                and ops.PROFILE is None)
 
     def begin_detached(self):
         """-> (caller's stream, engine stream): the engine stream is ordered behind everything the caller has enqueued (its
@@ -615,7 +606,7 @@ class Engine:
             cin1 = NUM_CH_DEC[i] + (NUM_CH_ENC[i - 1] if i > 0 else 0)
             w, b = self._wb(f'depth_decoder/upconv_{i}_1.conv.conv', NUM_CH_DEC[i], cin1, 9)
             fork = leaf is not None and 0 < i <= 3
-            ho = self._handoff if (fork and not self._capturing and ops.PROFILE is None) else None
+            ho = self._handoff if (fork and ops.PROFILE is None) else None
             if ho is not None:
                 ho.arm()          # the leaf stream is released by this convolution's own completion signal
             ops.conv2d(ws.x[i, 0], w, ws.x[i, 1], src_b=skip, shift=b, ksize=3, pad_mode=PAD_REFLECT, upsample_a=True,
@@ -652,7 +643,6 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     def forward(self, inputs: Dict[Any, torch.Tensor], *, train: bool, sample_w: torch.Tensor,
                 smooth_w: Optional[torch.Tensor], noise: Optional[Dict[int, torch.Tensor]] = None,
-                draw_noise: bool = True, keep_noise: bool = False,
                 reuse_frozen: bool = False, inputs_ready=None) -> Tuple[Dict[Any, torch.Tensor], torch.Tensor]:
         """One _process_batch (dpp.py:906-923).  `inputs` tensors must already live on the device.
 
@@ -669,8 +659,8 @@ class Engine:
             # below overwrite workspace the backward in flight still reads
             self._main.wait_event(self._train_done)
         # what the stages share: the call's arguments, the converted frames, and what the schedule leaves for the loss stage
-        c = SimpleNamespace(inputs=inputs, inputs_ready=inputs_ready, train=train, noise=noise, draw_noise=draw_noise,
-                            keep_noise=keep_noise, have_noise=False, id_ready=None)
+        c = SimpleNamespace(inputs=inputs, inputs_ready=inputs_ready, train=train, noise=noise, have_noise=False,
+                            id_ready=None)
         self._convert_inputs(c)
         B = c.B
         self._cu_enc, self._cu_dec = self.cu_limit(B, 'encoders'), self.cu_limit(B, 'decoders')
@@ -682,8 +672,7 @@ class Engine:
         c.memo_feats = self._memo_lookup(c.aug[0]) if (B == 1 and not c.reuse) else None
         if train:
             self._train_bufs(ws)
-        if self.fresh_outputs:
-            self._fresh_output_planes(ws, B)
+        self._fresh_output_planes(ws, B)
         self._networks(ws, c)
         self._loss_stage(ws, c, sample_w, smooth_w)
         ws.frozen_valid = True      # encoder features + identity maps of THESE inputs and encoder weights are held
@@ -736,7 +725,7 @@ class Engine:
 
     def _identity_and_noise(self, ws, c) -> bool:
         """Identity reprojection maps (dpp.py:1047-1052) and the tie-break noise depend on the inputs only.
-        -> whether ws.noise holds this forward's noise."""
+        -> whether ws.noise holds this forward's noise (injected); otherwise the loss kernel draws it."""
         if not c.reuse:
             # one launch per source frame straight from the caller's planes (stacking them first cost two 7 MB copies)
             ops.photo_map(c.rgb[-1], c.rgb[0], ws.idmap[0], None, c.B, c.B, self.H, self.W)
@@ -745,20 +734,14 @@ class Engine:
             for s in range(4):
                 ws.noise[s].copy_(c.noise[s])
             return True
-        if c.keep_noise:                     # already copied into ws.noise by the graph driver
-            return True
-        if c.draw_noise and self._capturing:
-            # a captured step replays fixed kernel arguments: torch's graph-safe generator keeps the draws fresh
-            ws.noise.normal_().mul_(1e-5)  # dpp.py:1055-1056
-            return True
         return False
 
     def _enqueue_identity(self, ws, c, wg) -> None:
         """_identity_and_noise() on the wgrad stream, idle during the forward; c.id_ready is recorded behind it."""
         if c.inputs_ready is not None:
             wg.wait_event(c.inputs_ready[3])
-        # (injected / captured noise is written by torch ops: they need torch's current stream switched)
-        with (torch.cuda.stream(wg) if (c.noise is not None or self._capturing) else ops.launch_on(wg)):
+        # (injected noise is written by torch ops: they need torch's current stream switched)
+        with (torch.cuda.stream(wg) if c.noise is not None else ops.launch_on(wg)):
             c.have_noise = self._identity_and_noise(ws, c)
         c.id_ready = torch.cuda.Event()
         c.id_ready.record(wg)
@@ -784,7 +767,7 @@ class Engine:
         # maps are out) -- for a single triplet only, where the step is a chain of dependent 5-15 us launches (K = 0, 192x640:
         # 1.454 -> 1.403 ms per frame incl. read-back).  At B = 5 the chip is throughput-bound and the six fork/join event
         # pairs cost more than the launches they hide (3.311 -> 3.377 ms).
-        ds_aux = wg if (B == 1 and not self._capturing) else None
+        ds_aux = wg if B == 1 else None
         # A host minibatch still crossing PCIe: the identity maps read the un-augmented frames, i.e. they wait for the WHOLE
         # upload -- and so would everything queued behind them on the wgrad stream.  With the downsample convolutions on that
         # stream (single triplets) the first stage entry of the depth encoder must not inherit that wait: the
@@ -837,8 +820,8 @@ class Engine:
             c.have_noise = self._identity_and_noise(ws, c)
         # all four scales in one launch; reprojection maps stay in registers, only the selected frame's
         # SSIM coefficients are kept for the backward
-        if c.have_noise or not c.draw_noise:
-            ops.photo_automask_pyramid(ws.warped, rgb[0], ws.idmap, ws.noise if c.have_noise else None, ws.sel,
+        if c.have_noise:
+            ops.photo_automask_pyramid(ws.warped, rgb[0], ws.idmap, ws.noise, ws.sel,
                                        ws.coef if c.train else None, ws.partial, B, H, W)
         else:
             # dpp.py:1055-1056 draws randn * 1e-5 on the compute device every scale, every step: here inside the kernel
@@ -876,7 +859,7 @@ class Engine:
         small kernel + a 1-byte read-back (~30 us) against the ~0.3 ms of launch-bound encoder it replaces; identity cannot
         be used -- slam.py hands the descriptor pass a device copy and adapt() a host tensor (slam.py:145, 300-309)."""
         m = self._memo
-        if (m is None or not self.descriptor_memo or self._capturing or m.version != self._packed_version
+        if (m is None or not self.descriptor_memo or m.version != self._packed_version
                 or m.x.shape != x.shape or m.x.device != x.device):
             return None
         # ONE look-up per descriptor pass: slam.py runs the pass (and reads its 512 numbers back, i.e. the stream is drained)
@@ -1023,31 +1006,44 @@ class Engine:
             else:
                 allreduce(self._g[lo:hi])
 
-    def backward(self, B: int, defer_reduce: bool = False, allreduce=None) -> None:
+    def backward(self, B: int, allreduce=None) -> None:
         """dL/d(trainable arena) for the last training forward; fills self._g (dpp.py:312).
-        defer_reduce: the caller promises that adam() follows directly (adapt(), single GPU): the batched reduction of the
-        gradient partials is left to adam(), which fuses it with the update; self._g is complete after THAT launch.
         allreduce: data-parallel mode -- callable(slice of the gradient arena) that sum-all-reduces it over the ranks on
         torch's current stream.  With it (and grad_buckets > 1) backward() exchanges the gradients itself, bucket by bucket
         (see __init__); self.grads_synced tells the caller so."""
         ops.PERSISTENT_CU_LIMIT = self.cu_limit(B, 'backward')
         ws = self._ws[B]
         t = ws.train
-        c = ws.ctx
-        H, W = self.H, self.W
-        feats = ws.dfeats
         self._main = torch.cuda.current_stream(self.device) if self.device.type == 'cuda' else None
         side, wg = self._side_streams()
+        self._enqueue_weight_transposes(t, wg)
+        self._loss_backward(ws, t, ws.ctx)
+        bucketed = allreduce is not None and self.grad_buckets > 1
+        # overlapped exchange: needs the tail stream, the side / wgrad streams and the per-bucket tables of a previous backward
+        overlap = (bucketed and self._use_tail() and side is not None and wg is not None
+                   and getattr(t, 'bucket_tables', None) is not None)
+        self.grads_synced = False
+        self._decoder_backwards(ws, t, B, side, allreduce if overlap else None)
+        self._reduce_tables(t)
+        self._finish_gradients(t, allreduce if bucketed else None, overlap)
+        self.grads_synced = bucketed
+
+    def _enqueue_weight_transposes(self, t, wg) -> None:
+        """_transpose_decoder_weights() on the wgrad stream, BEFORE the loss backward goes out on the main stream (it
+        overlaps it); t.wt_ready is recorded behind it.  Without a wgrad stream: in line, no event."""
         t.wt_ready = None
         if wg is None:
             self._transpose_decoder_weights(t)
-        else:
-            wg.wait_stream(self._main)
-            with self._on(wg):
-                self._transpose_decoder_weights(t)
-            t.wt_ready = torch.cuda.Event()
-            t.wt_ready.record(wg)
-        # loss -> disparity logits and pose-decoder output ----------------------------------------
+            return
+        wg.wait_stream(self._main)
+        with self._on(wg):
+            self._transpose_decoder_weights(t)
+        t.wt_ready = torch.cuda.Event()
+        t.wt_ready.record(wg)
+
+    def _loss_backward(self, ws, t, c) -> None:
+        """loss -> disparity logits (t.dz_disp) and pose-decoder output (t.dpose); records `inputs_released` behind them."""
+        H, W = self.H, self.W
         ops.loss_bwd2_pyramid(ws.disp, ws.sel, ws.coef, ws.warped, c.rgb[0], c.rgb[-1], c.rgb[1], c.Kinv, ws.P, c.sample_w,
                               t.ddisp_up, t.dp_partial, self.min_depth, self.max_depth)
         ops.disp_grad_pyramid(t.ddisp_up, ws.disp, c.aux if c.n_smooth else None, c.n_smooth, t.dz_disp, H, W)
@@ -1061,82 +1057,77 @@ class Engine:
             # it may overwrite its input buffers in place or drop them at once, like after the reference's synchronous step.
             self.inputs_released = torch.cuda.Event()
             self.inputs_released.record(self._main)
-        bucketed = allreduce is not None and self.grad_buckets > 1
-        # overlapped exchange: needs the tail stream, the side / wgrad streams and the per-bucket tables of a previous backward
-        overlap = (bucketed and self._use_tail() and side is not None and wg is not None
-                   and getattr(t, 'bucket_tables', None) is not None)
-        self.grads_synced = False
-        if side is not None:
-            main = self._main
-            side.wait_stream(main)
-            if t.wt_ready is not None:
-                side.wait_event(t.wt_ready)     # transposed pose_0 / pose_1 weights
-            with self._on(side):
-                self._backward_pose_decoder(ws, t, B, t.side)
-            if overlap and self.grad_buckets >= 3:
-                ev = torch.cuda.Event()
-                ev.record(side)                 # the pose decoder's three weight gradients + pose_2's are complete behind this
-                self._bucket_sync(t, 'pose', [ev], allreduce)
-            self._backward_depth_decoder(ws, t, B, mid_done=(lambda evs: self._bucket_sync(
-                t, 'mid' if self.grad_buckets >= 3 else 'early', evs, allreduce)) if overlap else None)
-            main.wait_stream(side)
-        else:
+
+    def _decoder_backwards(self, ws, t, B: int, side, exchange) -> None:
+        """Pose-decoder backward on the side stream beside the depth decoder's on the main stream (no side stream: one after
+        the other).  exchange: the all-reduce of an overlapped data-parallel exchange (else None) -- every bucket but the
+        last goes out on the tail stream as soon as its gradients are enqueued."""
+        if side is None:
             self._backward_depth_decoder(ws, t, B)
             self._backward_pose_decoder(ws, t, B, t)
-        # one batched, deterministic reduction of every weight / bias gradient partial into the arena
-        if t.table is None:
-            # (pose_2's gradients are written straight into the arena by pose_head_bwd: identity items, so that every
-            # trainable element is the output of exactly one item -- the fused reduction + Adam updates per item)
-            for key, n in (('pose_decoder/pose_2.weight', 12 * 256), ('pose_decoder/pose_2.bias', 12)):
-                sl = self._slot(self._g, key, n)
-                t.items.append((sl, sl, n, 1))
-            t.table = ops.make_reduce_table(t.items, self.device)
-            # the same items grouped by the bucket their destination lies in (every item reduces independently, in a fixed
-            # order: three launches give bitwise the single launch's arena)
-            base = self._g.data_ptr()
-            t.bucket_tables = {}
-            for name, lo, hi in self.bucket_ranges():
-                its = [it for it in t.items if lo <= (it[1].data_ptr() - base) // 4 < hi]
-                t.bucket_tables[name] = (ops.make_reduce_table(its, self.device), len(its), lo, hi)
-            assert sum(v[1] for v in t.bucket_tables.values()) == len(t.items)
-        self._pending_reduce = None
-        if bucketed:
-            ranges = self.bucket_ranges()
-            if overlap:
-                # the earlier buckets went out during the backward; the last one (level 4) is complete on the main stream now
-                name, lo, hi = ranges[-1]
-                if self.time_exchange:
-                    self.exchange_main_done = torch.cuda.Event(enable_timing=True)
-                    self.exchange_main_done.record(self._main)
-                self.tail_stream.wait_stream(self._main)
-                self._bucket_sync(t, name, [], allreduce)
-                self._tail_open = True
-            else:
-                # no overlap possible (first backward of this workspace, no tail / side streams, instrumented run): one
-                # reduction, then the SAME sequence of collectives on the same slices
-                if self._use_tail():
-                    self.tail_stream.wait_stream(self._main)
-                    with torch.cuda.stream(self.tail_stream):
-                        ops.reduce_multi(t.table, len(t.items), self._g)
-                        for name, lo, hi in ranges:
-                            allreduce(self._g[lo:hi])
-                    self._tail_open = True
-                else:
-                    ops.reduce_multi(t.table, len(t.items), self._g)
-                    for name, lo, hi in ranges:
-                        allreduce(self._g[lo:hi])
-            self.grads_synced = True
-        elif defer_reduce and self.fuse_adam and not self.data_parallel and not self._capturing and not self._use_tail():
-            self._pending_reduce = (t.table, len(t.items))
+            return
+        main = self._main
+        side.wait_stream(main)
+        if t.wt_ready is not None:
+            side.wait_event(t.wt_ready)     # transposed pose_0 / pose_1 weights
+        with self._on(side):
+            self._backward_pose_decoder(ws, t, B, t.side)
+        if exchange is not None and self.grad_buckets >= 3:
+            ev = torch.cuda.Event()
+            ev.record(side)                 # the pose decoder's three weight gradients + pose_2's are complete behind this
+            self._bucket_sync(t, 'pose', [ev], exchange)
+        self._backward_depth_decoder(ws, t, B, exchange)
+        main.wait_stream(side)
+
+    def _reduce_tables(self, t) -> None:
+        """Built once per workspace, after its first backward has registered every partial buffer in t.items: t.table (all
+        items: one batched, deterministic reduction of every weight / bias gradient partial into the arena) and
+        t.bucket_tables (the same items by gradient bucket)."""
+        if t.table is not None:
+            return
+        # pose_2's gradients are written straight into the arena by pose_head_bwd: identity items, so that every trainable
+        # element is the output of exactly one item and the table covers the whole arena
+        for key, n in (('pose_decoder/pose_2.weight', 12 * 256), ('pose_decoder/pose_2.bias', 12)):
+            sl = self._slot(self._g, key, n)
+            t.items.append((sl, sl, n, 1))
+        t.table = ops.make_reduce_table(t.items, self.device)
+        # the same items grouped by the bucket their destination lies in (every item reduces independently, in a fixed
+        # order: three launches give bitwise the single launch's arena)
+        base = self._g.data_ptr()
+        t.bucket_tables = {}
+        for name, lo, hi in self.bucket_ranges():
+            its = [it for it in t.items if lo <= (it[1].data_ptr() - base) // 4 < hi]
+            t.bucket_tables[name] = (ops.make_reduce_table(its, self.device), len(its), lo, hi)
+        assert sum(v[1] for v in t.bucket_tables.values()) == len(t.items)
+
+    def _finish_gradients(self, t, allreduce, overlap: bool) -> None:
+        """Partials -> gradient arena, then the exchange backward() owns.  allreduce: the bucketed data-parallel exchange
+        (None: single GPU, or the caller all-reduces the whole arena under training_stream())."""
+        ranges = self.bucket_ranges() if allreduce is not None else []
+        if overlap:
+            # the earlier buckets went out during the backward; the last one (level 4) is complete on the main stream now
+            if self.time_exchange:
+                self.exchange_main_done = torch.cuda.Event(enable_timing=True)
+                self.exchange_main_done.record(self._main)
+            self.tail_stream.wait_stream(self._main)
+            self._bucket_sync(t, ranges[-1][0], [], allreduce)
+            self._tail_open = True
         elif self._use_tail():
-            # the partial buffers are complete on the current stream; the reduction, the all-reduce (caller, under
-            # training_stream()) and Adam follow on the tail stream and nobody waits for them here
+            # the partial buffers are complete on the current stream; the reduction, the exchange (here in the engine's buckets,
+            # or the caller's under training_stream()) and Adam follow on the tail stream and nobody waits for them here
             self.tail_stream.wait_stream(self._main)
             with torch.cuda.stream(self.tail_stream):
-                ops.reduce_multi(t.table, len(t.items), self._g)
+                self._reduce_and_exchange(t, ranges, allreduce)
             self._tail_open = True
         else:
-            ops.reduce_multi(t.table, len(t.items), self._g)
+            self._reduce_and_exchange(t, ranges, allreduce)
+
+    def _reduce_and_exchange(self, t, ranges, allreduce) -> None:
+        """One reduction of the whole table, then (no overlap possible: first backward of this workspace, no tail / side
+        streams, instrumented run) the SAME sequence of collectives on the same slices as the overlapped exchange."""
+        ops.reduce_multi(t.table, len(t.items), self._g)
+        for _name, lo, hi in ranges:
+            allreduce(self._g[lo:hi])
 
     def _transpose_decoder_weights(self, t) -> None:
         """Flipped/transposed weights for every dgrad conv of the step (nine depth-decoder upconvs, pose_0 / pose_1).
@@ -1163,9 +1154,10 @@ class Engine:
             t.wt_table = ops.transpose_table(items)
         ops.weight_transpose_multi(t.wt_table, self._w)
 
-    def _backward_depth_decoder(self, ws, t, B: int, mid_done=None) -> None:
+    def _backward_depth_decoder(self, ws, t, B: int, exchange=None) -> None:
         """dgrad chain (critical path) on the current stream; every weight/bias gradient is independent
-        of the rest of the chain once its dz exists, so those run on a third stream (`wg_stream`)."""
+        of the rest of the chain once its dz exists, so those run on a third stream (`wg_stream`).
+        exchange: see _decoder_backwards -- the bucket of levels 0..3 goes out behind level 3."""
         H, W = self.H, self.W
         feats = ws.dfeats
         main = self._main
@@ -1178,20 +1170,19 @@ class Engine:
         # and the side stream (idle once the short pose-decoder backward is through): two wgrads in flight
         # instead of a serial tail after the dgrad chain.
         wg_streams = [wg] if (wg is None or side is None) else [wg, side]
-        counter = [0]
+        turn = itertools.cycle(wg_streams)      # whose turn the next weight-gradient launch is
+        ho = self._handoff if (wg is not None and ops.PROFILE is None) else None
+        behind_launch = 'armed' if ho is not None else 'record'
 
-        ho = self._handoff if (wg is not None and not self._capturing and ops.PROFILE is None) else None
-
-        def on_wg(fn, dep='record'):
-            """run fn on a wgrad stream.  dep: 'record' -- after everything enqueued so far on the main stream (an event
-            recorded there); 'armed' -- after the launch that took the hand-off event armed just before it (no marker packet on
-            the chain); None -- its inputs were complete before this function started (both wgrad streams are ordered behind
-            the loss backward by then)"""
+        def on_wg(fn, i, dep):
+            """run fn(i) on the wgrad stream whose turn it is.  dep: 'record' -- after everything enqueued so far on the main
+            stream (an event recorded there); 'armed' -- after the launch that took the hand-off event armed just before it (no
+            marker packet on the chain); None -- its inputs were complete before this function started (both wgrad streams are
+            ordered behind the loss backward by then)"""
             if wg is None:
-                fn()
+                fn(i)
                 return
-            st = wg_streams[counter[0] % len(wg_streams)]
-            counter[0] += 1
+            st = next(turn)
             if dep == 'armed':
                 ho.release(main, st)
             elif dep == 'record':
@@ -1199,7 +1190,31 @@ class Engine:
                 ev.record(main)
                 st.wait_event(ev)
             with self._on(st):
-                fn()
+                fn(i)
+
+        def disp_wgrad(i):      # dispconv_i weight + bias gradient partials
+            hi, wi, ci = H >> i, W >> i, NUM_CH_DEC[i]
+            if i not in t.disp_part:
+                nb = ops.dispconv_wgrad_blocks(B * hi * wi)
+                t.disp_part[i] = torch.empty(nb * (9 * ci + 1), device=self.device)
+                t.items.append((t.disp_part[i], self._slot(self._g, f'depth_decoder/dispconv_{i}.conv.weight', 9 * ci + 1),
+                                9 * ci + 1, nb))
+            ops.dispconv_wgrad(t.dz_disp[i], ws.x[i, 1], t.disp_part[i])
+
+        def upconv1_wgrad(i):   # upconv_i_1: input = cat(up(x[i,0]), feats[i-1])
+            hi, wi, ci = H >> i, W >> i, NUM_CH_DEC[i]
+            skip = feats[i - 1] if i > 0 else None
+            cin1 = ci + (NUM_CH_ENC[i - 1] if i > 0 else 0)
+            self._wgrad(t, (ws.x[i, 0], skip), (B, hi, wi, ci), t.dz[i, 1], f'depth_decoder/upconv_{i}_1.conv.conv', ci, cin1, 9,
+                        bias_blocks=ops.fold_blocks(B, hi, wi, ci, False), bias_partial=t.bias_part[i, 1],
+                        pad_mode=PAD_REFLECT, upsample_a=True)
+
+        def upconv0_wgrad(i):   # upconv_i_0: input = x[i+1,1] (or the frozen encoder feature for i == 4)
+            hi, wi, ci = H >> i, W >> i, NUM_CH_DEC[i]
+            src = ws.x[i + 1, 1] if i < 4 else feats[4]
+            cin0 = NUM_CH_ENC[-1] if i == 4 else NUM_CH_DEC[i + 1]
+            self._wgrad(t, (src, None), (B, hi >> 1, wi >> 1, ci), t.dz[i, 0], f'depth_decoder/upconv_{i}_0.conv.conv', ci, cin0, 9,
+                        bias_blocks=ops.fold_blocks(B, hi, wi, ci, True), bias_partial=t.bias_part[i, 0], pad_mode=PAD_REFLECT)
 
         if t.wt_ready is not None:
             main.wait_event(t.wt_ready)     # transposed dgrad weights (issued at the start of backward())
@@ -1211,50 +1226,26 @@ class Engine:
             if i <= 3:
                 # the dispconv head's data gradient is folded in by fold_act_grad below (no separate pass over dxp)
                 wd, _ = self._wb(f'depth_decoder/dispconv_{i}.conv', 1, ci, 9)
-
-                def disp_wgrad(i=i, hi=hi, wi=wi, ci=ci):   # dispconv weight + bias gradient partials
-                    if i not in t.disp_part:
-                        nb = ops.dispconv_wgrad_blocks(B * hi * wi)
-                        t.disp_part[i] = torch.empty(nb * (9 * ci + 1), device=self.device)
-                        t.items.append((t.disp_part[i], self._slot(self._g, f'depth_decoder/dispconv_{i}.conv.weight', 9 * ci + 1),
-                                        9 * ci + 1, nb))
-                    ops.dispconv_wgrad(t.dz_disp[i], ws.x[i, 1], t.disp_part[i])
                 # (reads dz_disp[i] -- the loss backward -- and the forward activation x[i,1] only)
-                on_wg(disp_wgrad, dep=None if ho is not None else 'record')
-            nb1 = ops.fold_blocks(B, hi, wi, ci, False)
+                on_wg(disp_wgrad, i, None if ho is not None else 'record')
             if ho is not None:
                 ho.arm()
             ops.fold_act_grad(dxp_in, ws.x[i, 1], t.dz[i, 1], h=hi, w=wi, ch=ci, border=1, pool=False, act=ACT_ELU,
                               bias_partial=t.bias_part[i, 1], disp_dz=t.dz_disp[i] if wd is not None else None,
                               disp_w=wd.view(9, ci) if wd is not None else None)
-            # upconv_i_1: input = cat(up(x[i,0]), feats[i-1])
-            skip = feats[i - 1] if i > 0 else None
-            cin1 = ci + (NUM_CH_ENC[i - 1] if i > 0 else 0)
-            on_wg(lambda i=i, hi=hi, wi=wi, ci=ci, skip=skip, cin1=cin1, nb1=nb1: self._wgrad(
-                t, (ws.x[i, 0], skip), (B, hi, wi, ci), t.dz[i, 1], f'depth_decoder/upconv_{i}_1.conv.conv', ci, cin1, 9,
-                bias_blocks=nb1, bias_partial=t.bias_part[i, 1], pad_mode=PAD_REFLECT, upsample_a=True),
-                dep='armed' if ho is not None else 'record')
-            wt = t.wt_dec[i, 1]
+            on_wg(upconv1_wgrad, i, behind_launch)
             dxa = t.dxp[1][:B * (hi + 2) * (wi + 2) * ci].view(B, hi + 2, wi + 2, ci)
-            ops.conv2d(t.dz[i, 1], wt, dxa, ksize=3, pad=2, cache=self._desc_cache, key=(id(self), 'dg', id(ws), i, 1))
-            nb0 = ops.fold_blocks(B, hi, wi, ci, True)
+            ops.conv2d(t.dz[i, 1], t.wt_dec[i, 1], dxa, ksize=3, pad=2, cache=self._desc_cache, key=(id(self), 'dg', id(ws), i, 1))
             if ho is not None:
                 ho.arm()
             ops.fold_act_grad(dxa, ws.x[i, 0], t.dz[i, 0], h=hi, w=wi, ch=ci, border=1, pool=True, act=ACT_ELU,
                               bias_partial=t.bias_part[i, 0])
-            # upconv_i_0: input = x[i+1,1] (or the frozen encoder feature for i == 4)
-            src = ws.x[i + 1, 1] if i < 4 else feats[4]
-            cin0 = NUM_CH_ENC[-1] if i == 4 else NUM_CH_DEC[i + 1]
-            h2, w2 = hi >> 1, wi >> 1
-            on_wg(lambda i=i, h2=h2, w2=w2, ci=ci, src=src, cin0=cin0, nb0=nb0: self._wgrad(
-                t, (src, None), (B, h2, w2, ci), t.dz[i, 0], f'depth_decoder/upconv_{i}_0.conv.conv', ci, cin0, 9,
-                bias_blocks=nb0, bias_partial=t.bias_part[i, 0], pad_mode=PAD_REFLECT),
-                dep='armed' if ho is not None else 'record')
+            on_wg(upconv0_wgrad, i, behind_launch)
             if i < 4:
-                wt = t.wt_dec[i, 0]
+                h2, w2, cin0 = hi >> 1, wi >> 1, NUM_CH_DEC[i + 1]
                 dxp_in = t.dxp[0][:B * (h2 + 2) * (w2 + 2) * cin0].view(B, h2 + 2, w2 + 2, cin0)
-                ops.conv2d(t.dz[i, 0], wt, dxp_in, ksize=3, pad=2, cache=self._desc_cache, key=(id(self), 'dg', id(ws), i, 0))
-            if i == 3 and mid_done is not None:
+                ops.conv2d(t.dz[i, 0], t.wt_dec[i, 0], dxp_in, ksize=3, pad=2, cache=self._desc_cache, key=(id(self), 'dg', id(ws), i, 0))
+            if i == 3 and exchange is not None:
                 # every gradient of levels 0..3 and of the four disparity heads has been enqueued: weight gradients on the
                 # wgrad streams, bias partials by the folds on the main stream.  Level 4 (53 % of the arena) is still to come.
                 evs = []
@@ -1262,7 +1253,7 @@ class Engine:
                     ev = torch.cuda.Event()
                     ev.record(st)
                     evs.append(ev)
-                mid_done(evs)
+                self._bucket_sync(t, 'mid' if self.grad_buckets >= 3 else 'early', evs, exchange)
         if wg is not None:
             main.wait_stream(wg)
 
@@ -1286,112 +1277,6 @@ class Engine:
         self._wgrad(t, (ws.pf4, None), (n2, h5, w5, 256), t.dz_sq, 'pose_decoder/squeeze', 256, 512, 1, pad=0)
 
     # ------------------------------------------------------------------------------------------
-    # hipGraph: the whole forward+backward of a training step (~130 kernel launches over three streams) can be
-    # captured and replayed as one graph.  Kept as an option; see graph_preferred() for why it is not the default.
-    GRAPH_KEYS = ([('rgb_aug', f, 0) for f in (-1, 0, 1)] + [('rgb', f, 0) for f in (-1, 0, 1)] +
-                  [('rgb', 0, s) for s in (1, 2, 3)] + [('camera_matrix', 0), ('inv_camera_matrix', 0),
-                                                        ('relative_distance', 0), ('relative_distance', 1)])
-
-    def graphs_enabled(self) -> bool:
-        return (self.device.type == 'cuda' and os.environ.get('CLSLAM_HIPGRAPH', 'auto') != '0' and ops.PROFILE is None)
-
-    def graph_preferred(self, B: int) -> bool:
-        """hipGraph replay of the step is opt-in (CLSLAM_HIPGRAPH=1).  Measured on MI355X / ROCm 7.2: replaying
-        the three-stream step costs 1.73 ms at B=1 and an erratic 2.2-3.6 ms at B=2 (a single-stream capture: 3.4 ms,
-        ~25 us per node) against 1.60 / 1.79 ms for eager launches once the per-launch Python cost was trimmed
-        (raw stream handle, pointer checks); at B >= 3 the step is GPU-bound either way (3.39 vs 4.0 ms)."""
-        return self.graphs_enabled() and os.environ.get('CLSLAM_HIPGRAPH', 'auto') == '1'
-
-    def train_step_graphed(self, inputs: Dict[Any, torch.Tensor], *, sample_w: torch.Tensor, smooth_w: Optional[torch.Tensor],
-                           noise: Optional[Dict[int, torch.Tensor]], copy_inputs: bool = True,
-                           reuse_frozen: bool = False, want_outputs: bool = True):
-        """forward(train=True) + backward() through a captured hipGraph (captured on first use per
-        batch size / noise mode; a second, encoder-free graph serves the reuse_frozen steps).  Returns
-        (outputs, losses) as fresh tensors."""
-        B = inputs['rgb_aug', 0, 0].shape[0]
-        key = (B, noise is not None, 0 if smooth_w is None else int(smooth_w.numel()))
-        st = self._graphs.get(key)
-        ws = self.workspace(B)
-        first = st is None
-        if first:
-            st = SimpleNamespace(graphs={}, inputs={}, sample_w=sample_w.clone(),
-                                 smooth_w=None if smooth_w is None else smooth_w.clone())
-            for k in self.GRAPH_KEYS:
-                v = inputs[k]
-                st.inputs[k] = (v.to(torch.float64) if k[0] == 'relative_distance' else self._img(v)).clone()
-            self._graphs[key] = st
-        # everything the replay reads goes into its static buffers with ONE launch (up to 15 + 2 + 4 torch copies
-        # otherwise: at B <= 2 their launch gaps were ~8 % of the step)
-        staged = [(sample_w, st.sample_w)]
-        if smooth_w is not None:
-            staged.append((smooth_w, st.smooth_w))
-        if copy_inputs and not first:
-            staged += [(inputs[k], st.inputs[k]) for k in self.GRAPH_KEYS]
-        if noise is not None:
-            staged += [(noise[s], ws.noise[s]) for s in range(4)]
-        self._stage(staged)
-        reuse = bool(reuse_frozen and not copy_inputs and self.reuse_frozen_features and getattr(ws, 'frozen_valid', False))
-        entry = st.graphs.get(reuse)
-        if entry is None:
-            entry = SimpleNamespace(graph=None, outputs=None, losses=None)
-
-            def run():
-                out, losses = self.forward(st.inputs, train=True, sample_w=st.sample_w, smooth_w=st.smooth_w,
-                                           noise=None, draw_noise=noise is None, keep_noise=noise is not None,
-                                           reuse_frozen=reuse)
-                self.backward(B)
-                return out, losses
-            fresh = self.fresh_outputs
-            self.fresh_outputs = False          # the graph writes into static planes; copies are handed out
-            self._capturing = True              # no asynchronous tail inside a captured step
-            self.wait_training()
-            try:
-                cur = torch.cuda.current_stream(self.device)
-                warm = torch.cuda.Stream(device=self.device)
-                warm.wait_stream(cur)
-                with torch.cuda.stream(warm):   # eager warm-up: allocates every workspace buffer
-                    run()
-                cur.wait_stream(warm)
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=self.capture_stream):
-                    entry.outputs, entry.losses = run()
-                entry.graph = g
-                st.graphs[reuse] = entry
-            finally:
-                self.fresh_outputs = fresh
-                self._capturing = False
-        self.wait_training()
-        entry.graph.replay()
-        ws.frozen_valid = True
-        # the graph writes static planes: hand out copies (skipped for the intermediate steps of adapt(steps=S),
-        # whose outputs the caller drops -- dpp.py:309-319 returns the last step's only)
-        losses = torch.empty_like(entry.losses)
-        handed = [(entry.losses, losses)]
-        outputs: Dict[Any, torch.Tensor] = {}
-        if want_outputs:
-            for k, v in entry.outputs.items():
-                outputs[k] = torch.empty(v.shape, dtype=v.dtype, device=v.device)
-                handed.append((v, outputs[k]))
-        self._stage(handed)
-        return outputs, losses
-
-    @staticmethod
-    def _stage(pairs) -> None:
-        """(src, dst) copies on the current stream: one clslam_copy_multi launch for the plain ones, torch's
-        copy_ for anything that needs a conversion (dtype, layout, host source)."""
-        plain = []
-        for src, dst in pairs:
-            if (src.dtype == dst.dtype and src.device == dst.device and src.shape == dst.shape and src.is_contiguous()
-                    and dst.is_contiguous()):
-                plain.append((src, dst))
-            elif src.shape == dst.shape or src.numel() == dst.numel():
-                dst.copy_(src.reshape(dst.shape), non_blocking=True)
-            else:
-                raise ClslamError(f'cannot stage {tuple(src.shape)} into {tuple(dst.shape)}')
-        ops.copy_multi(plain)
-
-    # ------------------------------------------------------------------------------------------
     def adam(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, guard: Optional[torch.Tensor] = None) -> None:
         """guard: the step's loss (1 element); a NaN there makes the kernel skip the update."""
         self.adam_step_count += 1
@@ -1405,13 +1290,7 @@ class Engine:
             self._tail_open = False
         else:
             self.wait_training()
-            if self._pending_reduce is not None:
-                table, nitems = self._pending_reduce
-                self._pending_reduce = None
-                ops.reduce_multi_adam(table, nitems, self._g, self._w, self._m, self._v, lr, self.adam_step_count, betas[0], betas[1],
-                                      eps, guard=guard)
-            else:
-                ops.adam_step(self._w, self._g, self._m, self._v, lr, self.adam_step_count, betas[0], betas[1], eps, guard=guard)
+            ops.adam_step(self._w, self._g, self._m, self._v, lr, self.adam_step_count, betas[0], betas[1], eps, guard=guard)
             self._tail_event = None
         self._modules_stale = True
 

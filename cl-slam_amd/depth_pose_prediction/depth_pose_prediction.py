@@ -399,19 +399,11 @@ class DepthPosePrediction:
                             eng._prealloc_armed = it == steps - 1      # the planes this call hands out: the caller's pool (below)
                             # steps 2..S see the same minibatch through the same frozen, eval-mode encoders (dpp.py:308-313):
                             # their features and the identity-reprojection maps are kept, only the decoders re-run
-                            if eng.graph_preferred(training_data['rgb_aug', 0, 0].shape[0]):
-                                # forward + backward replayed as one hipGraph (same kernels, same streams)
-                                outputs_eval, losses = self._process_batch(training_data, loss_weights, train=True, graphed=True,
-                                                                           copy_inputs=(it == 0), reuse_frozen=(it > 0),
-                                                                           want_outputs=(it == steps - 1))
-                                self.optimizer.zero_grad()
-                                self._reduce_gradients()
-                            else:
-                                outputs_eval, losses = self._process_batch(training_data, loss_weights, train=True,
-                                                                           reuse_frozen=(it > 0))
-                                self.optimizer.zero_grad()
-                                self._backward(training_data)
-                                released = eng.inputs_released if it == steps - 1 else None
+                            outputs_eval, losses = self._process_batch(training_data, loss_weights, train=True,
+                                                                       reuse_frozen=(it > 0))
+                            self.optimizer.zero_grad()
+                            self._backward(training_data)
+                            released = eng.inputs_released if it == steps - 1 else None
                             # dpp.py:1115-1118 aborts on a NaN loss before backward/step.  Checking there costs a full host
                             # sync in the middle of the step (the GPU idles while the host enqueues the backward), and a
                             # sync at the end of the step starves the GPU at the start of the next one.  Instead the
@@ -466,7 +458,7 @@ class DepthPosePrediction:
         ext[21] = 1.0
         dist.all_reduce(ext, group=group)
         eng._g.zero_()
-        if eng.grad_buckets > 1 and not eng.graph_preferred(1):
+        if eng.grad_buckets > 1:
             for _name, lo, hi in eng.bucket_ranges():
                 dist.all_reduce(eng._g[lo:hi], group=group)
         else:
@@ -476,11 +468,11 @@ class DepthPosePrediction:
 
     def _empty_shard_steps(self, steps: int):
         """adapt() of a data-parallel rank whose shard is empty: the same sequence of collectives as a rank with samples
-        (18 loss scalars, then the gradient arena -- in the engine's buckets, or whole on the hipGraph path), contributing
+        (18 loss scalars, then the gradient arena -- in the engine's buckets, or whole with CLSLAM_GRAD_BUCKETS=1), contributing
         zeros; the NaN check on the all-reduced loss and the guarded Adam step like everywhere else."""
         eng, dist, group = self.engine, self._dp['dist'], self._dp['group']
         eng.wait_training()
-        bucketed = eng.grad_buckets > 1 and not eng.graph_preferred(1)
+        bucketed = eng.grad_buckets > 1
         for _ in range(steps):
             ext = torch.cat([torch.zeros(18, device=self.device), self._dp_tag(0)])
             dist.all_reduce(ext, group=group)
@@ -822,22 +814,14 @@ class DepthPosePrediction:
         cur.wait_event(ev)      # the dict is device-resident from the caller's stream's point of view when the call returns
 
     def _process_batch(self, inputs: Dict[Any, Tensor], loss_sample_weights: Optional[Tensor] = None,
-                       use_online: bool = False, train: bool = False, graphed: bool = False, copy_inputs: bool = True,
-                       reuse_frozen: bool = False, want_outputs: bool = True):
+                       use_online: bool = False, train: bool = False, reuse_frozen: bool = False):
         ready = None
         if not reuse_frozen:             # steps 2..S of one adapt() call see the dict this loop already moved
             ready = self._upload(inputs)
         B = inputs['rgb_aug', 0, 0].shape[0]
         sample_w, smooth_w = self._sample_weights(B, loss_sample_weights, local=not train)
-        if graphed:
-            if ready is not None:
-                torch.cuda.current_stream(self.device).wait_event(ready[3])
-            outputs, losses = self.engine.train_step_graphed(inputs, sample_w=sample_w, smooth_w=smooth_w,
-                                                             noise=self._injected_noise, copy_inputs=copy_inputs,
-                                                             reuse_frozen=reuse_frozen, want_outputs=want_outputs)
-        else:
-            outputs, losses = self.engine.forward(inputs, train=train, sample_w=sample_w, smooth_w=smooth_w,
-                                                  noise=self._injected_noise, reuse_frozen=reuse_frozen, inputs_ready=ready)
+        outputs, losses = self.engine.forward(inputs, train=train, sample_w=sample_w, smooth_w=smooth_w,
+                                              noise=self._injected_noise, reuse_frozen=reuse_frozen, inputs_ready=ready)
         if ready is not None:
             self._upload_rest(inputs, ready[4])
         ext = None
@@ -847,7 +831,7 @@ class DepthPosePrediction:
             # Three extra scalars ride on the exchange: this rank's sample count and its gradient-exchange layout
             # (code, code^2) -- _check_dp_tag() raises when the shard sizes do not add up to the global batch every rank
             # scaled its loss weights by (a stale enable_data_parallel after the replay buffer grew), or when the ranks would
-            # issue different sequences of collectives (bucketed / whole / hipGraph), instead of corrupting or hanging silently.
+            # issue different sequences of collectives (bucketed / whole), instead of corrupting or hanging silently.
             ext = torch.cat([losses, self._dp_tag(B)])
             self._dp_posted += 1
             self._dp['dist'].all_reduce(ext, group=self._dp['group'])
@@ -890,7 +874,7 @@ class DepthPosePrediction:
         """(samples of this rank, c, c^2, failed): c = the gradient-exchange layout this rank will use for the step; failed = 1
         from a rank that could not run the step (_dp_abort_step)"""
         eng = self.engine
-        code = float(eng.grad_buckets * 2 + (1 if eng.graph_preferred(max(n_local, 1)) else 0))
+        code = float(eng.grad_buckets * 2)
         key = (n_local, code)
         hit = self._dp_tags.get(key)
         if hit is None:
@@ -908,8 +892,8 @@ class DepthPosePrediction:
                                f'batch of {self._dp["global_batch"]} (call it again whenever the minibatch size changes): the loss '
                                'weights of this step are wrong')
         if abs(world * c2 - c * c) > 1e-3:
-            raise RuntimeError('data-parallel step: the ranks disagree on the gradient-exchange layout (CLSLAM_GRAD_BUCKETS / '
-                               'CLSLAM_HIPGRAPH differ between processes)')
+            raise RuntimeError('data-parallel step: the ranks disagree on the gradient-exchange layout (CLSLAM_GRAD_BUCKETS '
+                               'differs between processes)')
 
     def _staged_losses(self) -> Dict[str, Tensor]:
         """the training step's loss dict: waits for the forward's staged copy only, not for the stream"""
@@ -935,8 +919,7 @@ class DepthPosePrediction:
 
     def _backward(self, inputs: Dict[Any, Tensor]) -> None:
         B = inputs['rgb_aug', 0, 0].shape[0]
-        # (adapt() calls optimizer.step() right after this: on a single GPU the reduction is fused into that launch)
-        self.engine.backward(B, defer_reduce=self._dp is None, allreduce=self._allreduce if self._dp is not None else None)
+        self.engine.backward(B, allreduce=self._allreduce if self._dp is not None else None)
         self._reduce_gradients()
 
     def _allreduce(self, t: Tensor) -> None:

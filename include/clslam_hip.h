@@ -41,9 +41,10 @@ extern "C" {
 /* ABI version: 101 = clslam_conv_desc.weight_wino appended, clslam_wino_weight_*; 100 -> 101 also covers the double* dp_partial of
  * the view-synthesis / loss backward and clslam_pose_bwd (round 4); 102 = clslam_conv_desc.cu_limit appended; 103 = clslam_handoff_* added;
  * 104 = per-scale range forms of the four pyramid launches added; 105 = clslam_depth_metrics* added; 106 = clslam_pcl_* added;
- * 107 = the range forms of 104 and the unfused pyramid backward removed; 108 = clslam_store_* added (frame store).
+ * 107 = the range forms of 104 and the unfused pyramid backward removed; 108 = clslam_store_* added (frame store);
+ * 109 = the batched-copy and the fused reduction + Adam entry points removed (DESIGN.md "Retired step paths").
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 108
+#define CLSLAM_ABI_VERSION 109
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -156,13 +157,6 @@ int clslam_reduce_partials(const float* partial, float* out, size_t n, int split
 /* Batched clslam_reduce_partials: items_dev is a DEVICE array of nitems records
  * {const float* partial; float* out; uint64_t n; int32_t splits; float scale} (32 bytes each).     */
 int clslam_reduce_multi(const void* items_dev, int nitems, int blocks_per_item, void* stream);
-/* clslam_reduce_multi followed, element by element, by the optimizer step of clslam_adam_step (torch.optim.Adam.step,
- * dpp.py:313) -- the single-GPU path, where nothing sits between the reduction and the update.  grad_base / param /
- * exp_avg / exp_avg_sq: the flat arenas (an item's `out` lies inside grad_base's; the same offset addresses the others);
- * every trainable element must be the output of exactly one item.  guard: see clslam_adam_step.                       */
-int clslam_reduce_multi_adam(const void* items_dev, int nitems, int blocks_per_item, const float* grad_base, float* param,
-                             float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, double eps, int step,
-                             const float* guard, void* stream);
 /* bias gradient: column sums of x[rows][ch], stage 1 (follow with clslam_reduce_partials).     */
 int clslam_colsum_blocks(int rows);
 int clslam_colsum(const float* x, float* partial, int rows, int ch, void* stream);
@@ -352,18 +346,6 @@ void* clslam_handoff_event_create(void);
 void clslam_handoff_event_destroy(void* event);
 int clslam_handoff_arm(void* event);
 int clslam_handoff_wait(void* event, void* producer_stream, void* consumer_stream);
-
-/* ---------------------------------------------------------------------------------------------
- * nitems independent device-to-device copies in one launch (items is a HOST array; sizes in bytes,
- * any alignment).  No reference counterpart: it replaces the per-tensor copies a hipGraph-replayed
- * step needs around the replay -- the sample dict of dpp.py:916-917 into the graph's static inputs and
- * the static output planes into the fresh tensors adapt()/predict() hand back (dpp.py:319).          */
-typedef struct clslam_copy_item {
-    const void* src;
-    void* dst;
-    size_t bytes;
-} clslam_copy_item;
-int clslam_copy_multi(const clslam_copy_item* items, int nitems, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Exact inner-product search = what the reference asks of faiss's
