@@ -17,6 +17,7 @@ OK = 0
 ACT_NONE, ACT_RELU, ACT_ELU, ACT_HSWISH, ACT_HSIGMOID = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
 DEPTH_EVAL_MEDIAN_SCALING, DEPTH_EVAL_FROM_DISP, DEPTH_EVAL_NO_MAX = 1, 2, 4
+TRAJ_MAX_POSES = 1 << 20             # include/clslam_hip.h CLSLAM_TRAJ_MAX_POSES
 
 fptr = C.c_void_p
 i32 = C.c_int32
@@ -160,9 +161,12 @@ _SIGNATURES = {
     'clslam_pcl_splat_scratch': [i32, i32],
     'clslam_pcl_splat': [fptr, fptr, fptr, i32, fptr, fptr, i32, i32, C.c_longlong, C.c_longlong, i32, C.c_double, i32, C.c_void_p],
     'clslam_pcl_resolve': [fptr, fptr, C.c_longlong, fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
+    'clslam_pose_pair_error': [fptr, fptr, i32, i32, fptr, C.c_void_p],
+    'clslam_traj_metrics_scratch': [i32],
+    'clslam_traj_metrics': [fptr, fptr, i32, i32, fptr, fptr, fptr, fptr, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
-ABI_VERSION = 109          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
+ABI_VERSION = 110          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32]}      # return size_t
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}

@@ -700,6 +700,68 @@ def depth_metrics(pred, gt, min_depth, max_depth, median_scaling=True, from_disp
     return out
 
 
+# ---- trajectory and pose-error metrics (csrc/traj_eval.hip; the evaluator's API is clslam_hip/traj_eval.py) ------------------
+def _poses(fn: str, name: str, t) -> None:
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or tuple(t.shape[1:]) != (4, 4) or t.dtype is not torch.float64:
+        raise _lib.ClslamError(f'{fn}: {name} must be a (n, 4, 4) float64 tensor, got '
+                               f'{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}')
+
+
+def pose_pair_error(a, b, a_inverted=False, out=None):
+    """a, b (n,4,4) fp64 -> (n,2) fp64 device tensor [translation_error, rotation_error (rad)] of inv(b_i) @ a_i, or of
+    inv(b_i) @ inv(a_i) with a_inverted (slam.py:257-259 / dpp.py:505-511)"""
+    fn = 'pose_pair_error'
+    _poses(fn, 'a', a)
+    _poses(fn, 'b', b)
+    n = a.shape[0]
+    if b.shape[0] != n or b.device != a.device:
+        raise _lib.ClslamError(f'{fn}: a {tuple(a.shape)} on {a.device} and b {tuple(b.shape)} on {b.device} must hold the same '
+                               'number of poses on one device')
+    if out is None:
+        out = torch.empty(n, 2, dtype=torch.float64, device=a.device)
+    elif tuple(out.shape) != (n, 2):
+        raise _lib.ClslamError(f'{fn}: out must be {(n, 2)}, got {tuple(out.shape)}')
+    _lib.get_lib().call('clslam_pose_pair_error', _pd(a), _pd(b), n, int(bool(a_inverted)), _pd(out), _stream(a))
+    return out
+
+
+def traj_metrics_scratch(n: int) -> int:
+    return _query('clslam_traj_metrics_scratch', n)
+
+
+def traj_segments(n: int) -> int:
+    """rows of the `segments` output: eight lengths for every tenth first frame (utils.py:225-230)"""
+    return (n + 9) // 10 * 8
+
+
+def traj_metrics(pred, gt, optimize_scale=False, out=None, segments=None, dist=None, pairs=None):
+    """pred, gt (n,4,4) fp64 -> (8,) fp64 device tensor [ave_t_err, ave_r_err, n_segments, ate, rpe_trans, rpe_rot, scaling,
+    path_length] (slam/utils.py:129-383).  Optional outputs: segments (ceil(n/10)*8, 6), dist (n), pairs (max(n-1, 0), 2) = the
+    RPE pair errors (copied out of the scratch)."""
+    fn = 'traj_metrics'
+    _poses(fn, 'pred', pred)
+    _poses(fn, 'gt', gt)
+    n = pred.shape[0]
+    if gt.shape[0] != n or gt.device != pred.device:
+        raise _lib.ClslamError(f'{fn}: pred {tuple(pred.shape)} on {pred.device} and gt {tuple(gt.shape)} on {gt.device} must hold '
+                               'the same number of poses on one device')
+    words = traj_metrics_scratch(n)
+    if words <= 0:
+        raise _lib.ClslamError(f'{fn}: {n} poses are beyond the kernel\'s range ({_lib.TRAJ_MAX_POSES})')
+    if out is None:
+        out = torch.empty(8, dtype=torch.float64, device=pred.device)
+    for name, t, shape in (('out', out, (8,)), ('segments', segments, (traj_segments(n), 6)), ('dist', dist, (n,)),
+                           ('pairs', pairs, (max(n - 1, 0), 2))):
+        if t is not None and tuple(t.shape) != shape:
+            raise _lib.ClslamError(f'{fn}: {name} must be {shape}, got {tuple(t.shape)}')
+    scratch = torch.empty(words, dtype=torch.float64, device=pred.device)
+    _lib.get_lib().call('clslam_traj_metrics', _pd(pred), _pd(gt), n, int(bool(optimize_scale)), _pd(out), _pd(segments), _pd(dist),
+                        _pd(scratch), _stream(pred))
+    if pairs is not None and n > 1:
+        pairs.copy_(scratch[8:8 + 2 * (n - 1)].view(n - 1, 2))
+    return out
+
+
 # ---- dense mapping (csrc/mapping.hip; the map's API is clslam_hip/mapping.py) -----------------------------------------------
 def _pl(t):
     return _pa(t, torch.int64)

@@ -349,6 +349,48 @@ class DepthPosePrediction:
         raise NotImplementedError('offline pre-training (dpp.py:219-289) is outside the MI355X hot path; '
                                   'pre-train with the reference and load the checkpoint here')
 
+    def _validation_loader(self):
+        """dpp.py:829-904, validation half: the loader over val_set, built from the reference's `datasets` package"""
+        valid_dataset_types = ['Kitti', 'Cityscapes', 'RobotCar']
+        if self.dataset_type not in valid_dataset_types:
+            raise ValueError(f'dataset_type must be one of {valid_dataset_types}')
+        import datasets      # the reference's package (datasets/kitti.py, cityscapes.py, robotcar.py): not part of this one
+        from torch.utils.data import DataLoader
+        args = (self.dataset_path, self.val_set, self.frame_ids, self.scales, self.height, self.width)
+        if self.dataset_type == 'Kitti':
+            val_dataset = datasets.Kitti(*args, with_mask=self.mask_dynamic)
+        elif self.dataset_type == 'Cityscapes':
+            val_dataset = datasets.Cityscapes(*args, with_mask=self.mask_dynamic)
+        else:
+            val_dataset = datasets.Robotcar(*args, with_mask=self.mask_dynamic, start_frame=500, end_frame=4000)
+        print(f'Validation samples: {len(val_dataset):>5}')
+        return DataLoader(val_dataset, self.batch_size, shuffle=False, num_workers=self.num_workers, pin_memory=True, drop_last=True)
+
+    def validate(self, data_loader=None) -> float:
+        """Compute the validation loss (dpp.py:321-342): eval mode, the forward-only _process_batch per batch, the mean of
+        losses['loss'].  data_loader: any iterable of batches as adapt() takes them; None builds (once) the validation loader like
+        dpp.py:871-904, which needs the reference's `datasets` package.  The loss scalars stay on the device and are read back
+        together at the end.  save_val_depth needs the reference's plotting save_prediction, which is not provided: it is skipped
+        with one warning."""
+        if not self.is_trained:
+            warnings.warn('The model has not been trained yet.', RuntimeWarning)
+        if data_loader is None:
+            if self.val_loader is None:
+                self.val_loader = self._validation_loader()
+            data_loader = self.val_loader
+        if self.save_val_depth and self.save_val_depth_batches > 0:
+            warnings.warn('save_val_depth: save_prediction (matplotlib plots) is not provided; no depth image is saved',
+                          RuntimeWarning)
+        self._set_eval()
+        self.engine.pack_if_needed()
+        loss = []
+        for sample_i in data_loader:
+            self._process_batch(sample_i, train=False)
+            loss.append(self._losses_dev[17:18].clone())
+        if not loss:
+            raise ValueError('validate: the data loader is empty')
+        return float(np.mean(torch.cat(loss).cpu().double().numpy()))          # the one read-back
+
     def adapt(self,
               online_data: Dict[Any, Tensor],
               training_data: Optional[Dict[Any, Tensor]] = None,
@@ -583,6 +625,55 @@ class DepthPosePrediction:
             metrics['med_scaling'] = med
             if print_results:
                 print(f'Scaling ratios | med: {med:.3f} | std: {np.std(ratios / med):.3f}')
+        return metrics
+
+    def compute_pose_error(self, print_results: bool = True, data_loader=None) -> Dict[str, float]:
+        """dpp.py:470-525 with the pair error on the device (ops.pose_pair_error).  data_loader: any iterable of sample dicts
+        holding ('rgb_aug', -1, 0), ('rgb_aug', 0, 0) and ('relative_pose', 0); None builds the validation set like dpp.py:474-491
+        (Kitti only), which needs the reference's `datasets` package.  Per sample the pose network runs and one launch writes
+        [translation error, rotation error] of inv(gt) @ inv(prediction) into a growing device buffer, which is read back once
+        at the end.  The pair error is formed in float64 from the float32 prediction; the reference forms it in float32.
+        -> {'rpe_trans': metres, 'rpe_rot': degrees (the mean of the per-sample degrees)}"""
+        if not self.is_trained:
+            warnings.warn('The model has not been trained yet.', RuntimeWarning)
+        from clslam_hip import ops
+        if data_loader is None:
+            if self.dataset_type != 'Kitti':
+                warnings.warn(f'Unsupported dataset: {self.dataset_type}', RuntimeWarning)
+                return {}
+            import datasets      # the reference's package (datasets/kitti.py): not part of this one
+            from torch.utils.data import DataLoader
+            dataset = datasets.Kitti(self.dataset_path, self.val_set, frame_ids=[-1, 0], scales=[0], height=self.height,
+                                     width=self.width, poses=True, with_depth=True)
+            data_loader = DataLoader(dataset, batch_size=1, shuffle=False, num_workers=self.num_workers, pin_memory=True,
+                                     drop_last=True)
+            print(f'Validation samples: {len(dataset):>5}')
+        rows = torch.empty(64, 2, dtype=torch.float64, device=self.device)
+        count = 0
+        for sample_i in data_loader:
+            pred, _ = self.predict_pose(sample_i['rgb_aug', -1, 0], sample_i['rgb_aug', 0, 0], as_numpy=False)
+            pred = pred.reshape(-1, 4, 4).double()
+            gt = sample_i['relative_pose', 0].to(self.device, torch.float64).reshape(-1, 4, 4).contiguous()
+            if gt.shape[0] != pred.shape[0]:
+                raise ValueError(f"('relative_pose', 0) holds {gt.shape[0]} poses for {pred.shape[0]} image pairs")
+            n = pred.shape[0]
+            if count + n > rows.shape[0]:
+                grown = torch.empty(max(2 * rows.shape[0], count + n), 2, dtype=torch.float64, device=self.device)
+                grown[:count] = rows[:count]
+                rows = grown
+            ops.pose_pair_error(pred, gt, a_inverted=True, out=rows[count:count + n])
+            count += n
+        if not count:
+            raise ValueError('compute_pose_error: the data loader is empty')
+        res = rows[:count].cpu().numpy()          # the one read-back
+        rpe_trans, rpe_rot = 0, 0
+        for trans_error, rot_error in res:        # dpp.py:513-519: running Python sums, degrees per sample
+            rpe_trans += float(trans_error)
+            rpe_rot += float(rot_error) * 180 / np.pi
+        metrics = {'rpe_trans': rpe_trans / count, 'rpe_rot': rpe_rot / count}
+        if print_results:
+            for key, value in metrics.items():
+                print(f'{key:<8}: {value:>6.3f}')
         return metrics
 
     def predict_pose(

@@ -42,9 +42,10 @@ extern "C" {
  * the view-synthesis / loss backward and clslam_pose_bwd (round 4); 102 = clslam_conv_desc.cu_limit appended; 103 = clslam_handoff_* added;
  * 104 = per-scale range forms of the four pyramid launches added; 105 = clslam_depth_metrics* added; 106 = clslam_pcl_* added;
  * 107 = the range forms of 104 and the unfused pyramid backward removed; 108 = clslam_store_* added (frame store);
- * 109 = the batched-copy and the fused reduction + Adam entry points removed (DESIGN.md "Retired step paths").
+ * 109 = the batched-copy and the fused reduction + Adam entry points removed (DESIGN.md "Retired step paths");
+ * 110 = clslam_pose_pair_error, clslam_traj_metrics* added.
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 109
+#define CLSLAM_ABI_VERSION 110
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -563,6 +564,43 @@ int clslam_pcl_splat(const float* points, const long long* offsets, const double
                      double min_z, int clear, void* stream);
 int clslam_pcl_resolve(const float* points, const unsigned long long* zbuf, long long point_base, float* image, float* dist,
                        long long* index, int rows, int cols, int merge, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Trajectory and pose-error metrics (csrc/traj_eval.hip).  Poses are (n,4,4) row-major fp64 on the device, all arithmetic is
+ * double, every reduction runs in a fixed order (no floating-point atomics: two launches agree bitwise).  Every 4x4 inverse is
+ * a GENERAL inverse (LU with partial pivoting), as np.linalg.inv is in the reference: the rotation blocks need not be
+ * orthonormal.  A singular matrix gives non-finite results.  rotation_error(m) = acos(clamp(0.5 * (m00 + m11 + m22 - 1), -1, 1))
+ * (slam/utils.py:191-203), translation_error(m) = sqrt(m03^2 + m13^2 + m23^2) (utils.py:206-217).
+ *
+ * clslam_pose_pair_error: out (n,2) = [translation_error, rotation_error (rad)] of inv(b_i) @ (a_inverted ? inv(a_i) : a_i).
+ * a_inverted = 0 is slam.py:257-259 (a = the predicted transformation, b = the ground truth); a_inverted = 1 is dpp.py:505-511
+ * (compute_pose_error inverts the prediction first).  n = 0 is a no-op.
+ *
+ * clslam_traj_metrics replaces slam/utils.py:129-383 (calc_error and everything it calls) for n <= CLSLAM_TRAJ_MAX_POSES poses:
+ * out (8) = [ave_t_err, ave_r_err, n_segments, ate, rpe_trans, rpe_rot, scaling, path_length].
+ *   dist[i] = the path length of gt up to pose i (utils.py:164-172; a hierarchical sum, serial at every level: non-decreasing).
+ *   Segments (utils.py:220-250): for every first_frame = 0, 10, 20, ... < n and length = 100, 200, ..., 800 m, last_frame = the
+ *   first i >= first_frame with dist[i] > dist[first_frame] + length; pose_error = inv(inv(pred[first]) @ pred[last]) @
+ *   (inv(gt[first]) @ gt[last]).  ave_t_err / ave_r_err = the means of translation_error / length and rotation_error / length
+ *   over the segments that have a last frame, (0, 0) when none has (utils.py:292-314); n_segments = their number.
+ *   ate = sqrt(mean |gt_xyz - pred_xyz|^2) (utils.py:317-328; NaN for n = 0).  rpe_trans / rpe_rot = the means over i < n-1 of
+ *   the two errors of inv(inv(gt[i]) @ gt[i+1]) @ (inv(pred[i]) @ pred[i+1]) (utils.py:331-354; NaN for n < 2).
+ *   scaling = sum(pred_xyz * gt_xyz) / sum(pred_xyz^2) (utils.py:151-161), always reported (NaN for n = 0); both sums are added
+ *   in the order np.sum adds the contiguous (n,3) arrays (numpy's pairwise summation, products rounded on their own), so the
+ *   factor is the reference's to the last bit -- calc_error prints all its digits.  With optimize_scale != 0 the
+ *   translations of pred are multiplied by it for the SEGMENT errors only; ate and rpe use pred as given (utils.py:374,378).
+ *   path_length = dist[n-1].
+ * Optional outputs: segments (ceil(n/10)*8, 6), one row per (first_frame, length) in the reference's loop order:
+ * [first_frame, rotation_error / length, translation_error / length, length, speed = length / (0.1 * (last - first + 1)),
+ * last_frame]; a segment without a last frame has last_frame = -1 and NaN in the two errors and the speed.  dist (n).
+ * scratch: clslam_traj_metrics_scratch(n) doubles (0 = n out of range), 8-byte aligned, contents irrelevant on entry; after the
+ * call its doubles [8, 8 + 2n) hold, for tests and tools, the rows [translation_error, rotation_error] of the RPE pair
+ * (i, i+1) (zeros in row n-1).                                                                                                  */
+#define CLSLAM_TRAJ_MAX_POSES (1 << 20)
+int clslam_pose_pair_error(const double* a, const double* b, int n, int a_inverted, double* out, void* stream);
+int clslam_traj_metrics_scratch(int n);
+int clslam_traj_metrics(const double* pred, const double* gt, int n, int optimize_scale, double* out, double* segments,
+                        double* dist, double* scratch, void* stream);
 
 #ifdef __cplusplus
 }
