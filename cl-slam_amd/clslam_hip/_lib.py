@@ -59,6 +59,12 @@ class StoreGatherDesc(C.Structure):
                 ('n_frames', i32), ('n_levels', i32), ('capacity', i32), ('slot_bytes', C.c_int64)]
 
 
+class RingGatherDesc(C.Structure):
+    _fields_ = [('rgb', fptr * STORE_MAX_PLANES), ('aug', fptr * STORE_MAX_PLANES), ('offset', C.c_int64 * STORE_MAX_PLANES),
+                ('h', i32 * STORE_MAX_PLANES), ('w', i32 * STORE_MAX_PLANES), ('slot', i32 * STORE_MAX_PLANES),
+                ('n_frames', i32), ('n_levels', i32), ('capacity', i32), ('slot_bytes', C.c_int64)]
+
+
 # name -> argtypes (restype is always int unless listed in _RESTYPES)
 _SIGNATURES = {
     'clslam_version': [],
@@ -130,6 +136,9 @@ _SIGNATURES = {
     'clslam_color_jitter_f32': [fptr, fptr, C.c_void_p, fptr, i32, i32, i32, C.c_void_p],
     'clslam_store_pack': [C.POINTER(StorePackDesc), C.c_void_p, C.c_void_p, C.c_void_p],
     'clslam_store_gather_jitter': [C.POINTER(StoreGatherDesc), C.c_void_p, C.c_void_p, C.c_void_p, fptr, i32, i32, C.c_void_p],
+    'clslam_resize_level_u8': [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, i32,
+                               i32, i32, i32, i32, i32, i32, C.c_void_p],
+    'clslam_ring_gather': [C.POINTER(RingGatherDesc), C.c_void_p, C.c_void_p],
     'clslam_avgpool_chunks': [i32],
     'clslam_global_avgpool': [fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
     'clslam_se_gate': [fptr, fptr, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
@@ -166,7 +175,7 @@ _SIGNATURES = {
     'clslam_traj_metrics': [fptr, fptr, i32, i32, fptr, fptr, fptr, fptr, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
-ABI_VERSION = 110          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
+ABI_VERSION = 111          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32]}      # return size_t
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}

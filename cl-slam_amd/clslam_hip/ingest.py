@@ -596,3 +596,275 @@ def cat_dict(online: Dict, replay: Dict, device=None) -> Dict:
             dev = device if device is not None else (b.device if b.device.type != 'cpu' else a.device)
             out[k] = torch.cat([a.to(dev, non_blocking=True), b.to(dev, non_blocking=True)])
     return out
+
+
+# ======================================================================================================================
+# The driver's ONLINE sample on the GPU: `online_data = next(self.online_dataloader_iter)` (slam/slam.py:141) runs the dataset's
+# __getitem__ (datasets/kitti.py:231-317) on the driver's thread in front of every frame -- three PNGs, three four-level LANCZOS
+# chains, 24 ToTensor planes -- although sample t + 1 shares two of its three frames with sample t.
+class FrameRing:
+    """One uint8 allocation of `capacity` slots, one FRAME per slot: per level s of `scales` an interleaved (H>>s, W>>s, 3) image
+    at a fixed offset, ``slot_bytes`` = sum of 3 * (H>>s) * (W>>s).  ``put`` builds a frame's pyramid once -- one
+    clslam_resize_level_u8 launch per level, level 0 from the uploaded raw frame, level s from level s - 1 inside the slot
+    (datasets/kitti.py:258, datasets/utils.py:160-163) -- and ``gather`` writes the float planes of a sample from the slots of its
+    frames in one launch.  The oldest slot is reused first.  Every kernel runs on the caller's current stream."""
+
+    def __init__(self, height: int, width: int, scales: Sequence[int] = (0, 1, 2, 3), capacity: int = 8, device=None) -> None:
+        self.height, self.width, self.scales = int(height), int(width), tuple(int(s) for s in scales)
+        if self.scales != tuple(range(len(self.scales))) or not self.scales:
+            raise ValueError(f'FrameRing: scales = {tuple(scales)}; every level is built from the one above it, so they must be 0, 1, 2, ...')
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError(f'FrameRing: capacity = {capacity}')
+        self.device = torch.device('cuda' if device is None else device)
+        self.sizes = [(self.height >> s, self.width >> s) for s in self.scales]
+        self.offsets, off = [], 0
+        for h, w in self.sizes:
+            self.offsets.append(off)
+            off += 3 * h * w
+        self.slot_bytes = off
+        self._data = torch.zeros(self.capacity * self.slot_bytes, dtype=torch.uint8, device=self.device)
+        self._slots: Dict = {}                          # key -> slot, oldest first
+        self._free = list(range(self.capacity - 1, -1, -1))
+        self._pyramid = ImagePyramid(height, width, self.scales)       # its cache of tap plans
+
+    def __contains__(self, key) -> bool:
+        return key in self._slots
+
+    def __len__(self) -> int:
+        return len(self._slots)
+
+    def slot_of(self, key) -> int:
+        return self._slots.get(key, -1)
+
+    def level(self, key, scale: int) -> torch.Tensor:
+        """the (h, w, 3) uint8 image of `key` at `scale`: a view into the ring (debug / test read)"""
+        li = self.scales.index(scale)
+        h, w = self.sizes[li]
+        at = self._slots[key] * self.slot_bytes + self.offsets[li]
+        return self._data[at:at + 3 * h * w].view(h, w, 3)
+
+    def put(self, key, raw_u8: torch.Tensor, keep=()) -> int:
+        """raw_u8: the decoded frame, (Hraw, Wraw, 3) uint8 on the ring's device -> its slot.  The oldest slot whose key is not in
+        `keep` (the other frames of the sample being assembled) is reused when none is free."""
+        if raw_u8.dtype != torch.uint8 or raw_u8.dim() != 3 or raw_u8.shape[-1] != 3:
+            raise _lib.ClslamError(f'FrameRing.put expects an (H,W,3) uint8 frame, got {tuple(raw_u8.shape)} {raw_u8.dtype}')
+        slot = self._slots.pop(key, None)
+        if slot is None:
+            if not self._free:
+                oldest = next((k for k in self._slots if k not in keep), None)
+                if oldest is None:
+                    raise _lib.ClslamError(f'FrameRing: all {self.capacity} slots are held by the sample being assembled')
+                self._free.append(self._slots.pop(oldest))
+            slot = self._free.pop()
+        base = slot * self.slot_bytes
+        src = raw_u8.contiguous().unsqueeze(0)
+        for li, (h, w) in enumerate(self.sizes):
+            dst = self._data[base + self.offsets[li]:base + self.offsets[li] + 3 * h * w]
+            _, sh, sw, _ = src.shape
+            ops.resize_level_u8(src, dst, h, w, self._pyramid._plan(sw, w, self.device) if sw != w else None,
+                                self._pyramid._plan(sh, h, self.device) if sh != h else None)
+            src = dst.view(1, h, w, 3)
+        self._slots[key] = slot
+        return slot
+
+    def gather(self, keys, rgb, aug) -> None:
+        """rgb / aug [frame index * levels + level index] (contiguous float tensors of 3 * h * w values) <- byte / 255 of the frames
+        stored under `keys`, one launch"""
+        ops.ring_gather(self._data, self.slot_bytes, self.offsets, self.sizes, [self._slots[k] for k in keys], rgb, aug)
+
+
+class _OnlineIterator:
+    """what iter(DataLoader(dataset, batch_size=1)) is to slam/slam.py:141: sample(0), sample(1), ..., then StopIteration"""
+
+    def __init__(self, builder: 'OnlineSampleBuilder') -> None:
+        self._builder, self._next, self._len = builder, 0, len(builder.dataset)
+
+    def __iter__(self):
+        return self
+
+    def __len__(self) -> int:
+        return self._len
+
+    def __next__(self):
+        if self._next >= self._len:
+            raise StopIteration
+        self._next += 1
+        return self._builder.sample(self._next - 1)
+
+
+class OnlineSampleBuilder:
+    """The reference driver's online sample with its pixels on the GPU.
+
+        online = OnlineSampleBuilder(slam.online_dataset)        # the reference's Kitti / Robotcar object
+        online.install(slam)                                     # slam.step() runs unchanged
+
+    ``sample(i)`` is ``default_collate([dataset[i]])`` (what the driver's DataLoader(batch_size=1) yields) with the 24 image entries
+    as fresh (1,3,h,w) float32 tensors on `device`, bitwise the dataset's; the other entries are formed from the dataset's own
+    attributes like datasets/kitti.py:263-274,302-314 and `_preprocess` (:348-353) form them and stay on the host.  Each PNG is
+    decoded once (ahead of time on a small thread pool: Pillow's decoder releases the GIL), uploaded once from page-locked memory,
+    its pyramid is built once into a FrameRing slot by four launches, and a sample is one launch.
+
+    Covers the driver's configuration (slam/slam.py:44-72): no augmentation, one view, neither masks nor ground-truth depth;
+    anything else raises ValueError here, not at the first frame.  Kitti and Robotcar expose the same attributes
+    (datasets/robotcar.py:220-270 is kitti.py:231-317 without the depth branch) and go through the same code."""
+
+    _NEEDS = ('frame_ids', 'scales', 'height', 'width', 'camera_matrix', 'relative_distances', '_pre_getitem', '_scale_camera_matrix')
+
+    def __init__(self, dataset, device='cuda', ring_frames: int = 8, prefetch: int = 2, decode_threads: int = 2) -> None:
+        for name in self._NEEDS:
+            if not hasattr(dataset, name):
+                raise ValueError(f'OnlineSampleBuilder: the dataset has no `{name}` (a datasets.Kitti / Robotcar object is expected)')
+        if getattr(dataset, 'do_augmentation', False):
+            raise ValueError('OnlineSampleBuilder: do_augmentation=True (flip and colour jitter) is not covered; the driver builds its '
+                             'online dataset with do_augmentation=False')
+        if getattr(dataset, 'with_mask', False):
+            raise ValueError('OnlineSampleBuilder: with_mask=True is not covered')
+        if getattr(dataset, 'with_depth', False):
+            raise ValueError('OnlineSampleBuilder: with_depth=True is not covered')
+        if len(getattr(dataset, 'views', ('left',))) != 1:
+            raise ValueError(f'OnlineSampleBuilder: views={tuple(dataset.views)}: one view is covered')
+        scales = tuple(dataset.scales)
+        if not scales or scales != tuple(range(len(scales))):
+            raise ValueError(f'OnlineSampleBuilder: scales={scales}: the pyramid levels 0, 1, 2, ... are covered')
+        self.dataset = dataset
+        self.frame_ids = tuple(dataset.frame_ids)
+        self.scales = scales
+        if len(self.frame_ids) * len(scales) > _lib.STORE_MAX_PLANES:
+            raise ValueError(f'OnlineSampleBuilder: frame_ids={self.frame_ids} x scales={scales}: at most {_lib.STORE_MAX_PLANES} planes')
+        if int(ring_frames) < len(self.frame_ids):
+            raise ValueError(f'OnlineSampleBuilder: ring_frames={ring_frames} cannot hold the {len(self.frame_ids)} frames of one sample')
+        self.device = torch.device(device)
+        self.ring = FrameRing(dataset.height, dataset.width, scales, ring_frames, self.device)
+        self.prefetch = max(int(prefetch), 0)
+        self.decode_threads = max(int(decode_threads), 1)
+        self._pool = None
+        self._decoded: Dict = {}                        # path -> Future of the decoded (page-locked) frame, oldest first
+        self._matrices = None
+        self._per_sample = sum(3 * h * w for h, w in self.ring.sizes) * len(self.frame_ids)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def _decode_file(self, path) -> torch.Tensor:
+        import numpy as np
+        from PIL import Image
+        img = torch.from_numpy(np.asarray(Image.open(path).convert('RGB')).copy())            # datasets/kitti.py:249
+        return img.pin_memory() if self.device.type == 'cuda' else img
+
+    def _submit(self, path) -> None:
+        if path in self._decoded or path in self.ring:
+            return
+        if self._pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=self.decode_threads, thread_name_prefix='clslam-online-png')
+        while len(self._decoded) >= self.prefetch + 3:                    # the bound on decoded frames held
+            self._decoded.pop(next(iter(self._decoded))).cancel()
+        self._decoded[path] = self._pool.submit(self._decode_file, path)
+
+    def _paths(self, index: int):
+        img_filenames, _, shifted, _, _ = self.dataset._pre_getitem(index)
+        return [str(img_filenames[shifted + f]) for f in self.frame_ids], shifted
+
+    def _ensure(self, paths) -> None:
+        """every frame of `paths` into the ring: decode (the misses of one sample concurrently), one pinned upload, four launches"""
+        misses = [p for p in dict.fromkeys(paths) if p not in self.ring]
+        if len(misses) > 1 and self.decode_threads > 1:
+            for p in misses:
+                self._submit(p)
+        for p in misses:
+            fut = self._decoded.pop(p, None)
+            raw = self._decode_file(p) if fut is None or fut.cancelled() else fut.result()
+            self.ring.put(p, raw.to(self.device, non_blocking=True), keep=paths)
+
+    def _host_item(self, shifted: int) -> Dict:
+        """the non-image entries of dataset[index], un-collated, in the dataset's key order"""
+        ds = self.dataset
+        if self._matrices is None:                                        # kitti.py:263-267: the same matrices for every index
+            self._matrices = [ds._scale_camera_matrix(ds.camera_matrix, s) for s in range(len(self.scales))]
+        item = {('index'): shifted}
+        for s, (camera_matrix, inv_camera_matrix) in enumerate(self._matrices):
+            item['camera_matrix', s] = torch.from_numpy(camera_matrix.copy())                # _preprocess :348-349
+            item['inv_camera_matrix', s] = torch.from_numpy(inv_camera_matrix.copy())
+        for f in self.frame_ids[1:]:
+            item['relative_distance', f] = ds.relative_distances[shifted + f]                # kitti.py:303-304
+        if getattr(ds, 'include_poses', False):
+            for f in self.frame_ids[1:]:                                                     # kitti.py:306-314, ToTensor of a (4,4) array
+                item['relative_pose', f] = _array_to_tensor(ds.relative_poses[shifted + f])
+                item['absolute_pose', f] = _array_to_tensor(ds.global_poses[shifted + f])
+        return item
+
+    def _build(self, index: int, collated: bool) -> Dict:
+        from torch.utils.data import default_collate
+        paths, shifted = self._paths(index)
+        self._ensure(paths)
+        block = torch.empty(2 * self._per_sample, device=self.device)
+        shape = (lambda h, w: (1, 3, h, w)) if collated else (lambda h, w: (3, h, w))
+        rgb, aug, at = [], [], 0
+        for group in (rgb, aug):
+            for _ in self.frame_ids:
+                for h, w in self.ring.sizes:
+                    group.append(block[at:at + 3 * h * w].view(shape(h, w)))
+                    at += 3 * h * w
+        self.ring.gather(paths, rgb, aug)
+        host = self._host_item(shifted)
+        if collated:
+            host = default_collate([host])
+        # the dataset's key order: index, level 0 of every frame, the host entries, the lower levels, then every rgb_aug
+        nl = len(self.scales)
+        item = {('index'): host.pop('index')}
+        for j, f in enumerate(self.frame_ids):
+            item['rgb', f, 0] = rgb[j * nl]
+        item.update(host)
+        for j, f in enumerate(self.frame_ids):
+            for li in range(1, nl):
+                item['rgb', f, self.scales[li]] = rgb[j * nl + li]
+        for key in [k for k in item if isinstance(k, tuple) and k[0] == 'rgb']:
+            _, f, s = key
+            item['rgb_aug', f, s] = aug[self.frame_ids.index(f) * nl + self.scales.index(s)]
+        return item
+
+    def sample(self, index: int) -> Dict:
+        """the collated dict the driver gets from its DataLoader(batch_size=1) for `index`"""
+        out = self._build(index, collated=True)
+        n = len(self.dataset)
+        for nxt in range(index + 1, min(index + 1 + self.prefetch, n)):      # decode ahead: the frames of the next samples
+            for p in self._paths(nxt)[0]:
+                self._submit(p)
+        return out
+
+    def item(self, index: int) -> Dict:
+        """``dataset[index]`` (un-collated): what slam/slam.py:228 reads for a loop-closure candidate"""
+        return self._build(index, collated=False)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def install(self, slam) -> 'OnlineSampleBuilder':
+        """Switch the REFERENCE's driver object over: ``slam.online_dataloader_iter`` becomes an iterator over sample(0), sample(1),
+        ... (slam/slam.py:141), and ``slam.online_dataset`` gets a subclass of its own class, created here, whose __getitem__ is
+        item() (slam/slam.py:228: a dunder is looked up on the type, not on the instance).  The dataset's class itself and every
+        other instance keep their code.  Calling install() again rewinds the iterator and does not nest the subclass."""
+        if slam.online_dataset is not self.dataset:
+            raise ValueError('OnlineSampleBuilder.install: slam.online_dataset is not the dataset this builder was made for')
+        builder = self
+        base = getattr(type(self.dataset), '_clslam_online_base', type(self.dataset))
+
+        def getitem(_self, index):
+            return builder.item(index)
+        self.dataset.__class__ = type(base.__name__, (base,), {'__getitem__': getitem, '_clslam_online_base': base,
+                                                               '__module__': base.__module__})
+        slam.online_dataloader_iter = _OnlineIterator(self)
+        return self
+
+    def close(self) -> None:
+        """shut the PNG decode pool down and forget the frames decoded ahead"""
+        for fut in self._decoded.values():
+            fut.cancel()
+        self._decoded.clear()
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+
+def _array_to_tensor(value) -> torch.Tensor:
+    """torchvision's ToTensor of a 2-D numpy array that is no uint8 image (datasets/utils.py:213-215 on a (4,4) pose): (1,4,4),
+    dtype kept, nothing scaled"""
+    import numpy as np
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(value)[None]))

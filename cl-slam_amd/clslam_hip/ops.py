@@ -956,3 +956,47 @@ def store_gather_jitter(store: torch.Tensor, slot_bytes: int, offsets, sizes, n_
     partial = torch.empty(n_levels * max(n_img, 1) * 64, device=store.device) if aug is not None else None
     _lib.get_lib().call('clslam_store_gather_jitter', C.byref(desc), _pa(store, torch.uint8), _pa(slot_idx, torch.int32),
                         None if aug is None else _pa(params, torch.uint8), _p(partial), n_img, int(row0), _stream(store))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Online ingest: ring of per-frame uint8 pyramids (clslam_resize_level_u8, clslam_ring_gather, include/clslam_hip.h)
+def resize_level_u8(src: torch.Tensor, dst: torch.Tensor, out_h: int, out_w: int, plan_h, plan_v, pitch: Optional[int] = None) -> None:
+    """src (N,h,w,3) uint8 -> the bytes of `dst` (flat uint8, starting at the first output pixel) as (N,out_h,out_w,3) with `pitch`
+    bytes per row (default out_w * 3): Pillow's LANCZOS resize, both passes in one launch.  plan_h / plan_v = (bounds, coeffs,
+    ksize) on the device for w -> out_w / h -> out_h, None for an axis that keeps its size."""
+    if src.dim() != 4 or src.shape[-1] != 3:
+        raise _lib.ClslamError(f'resize_level_u8 expects (N,h,w,3) uint8 frames, got {tuple(src.shape)}')
+    N, h, w, _ = src.shape
+    pitch = out_w * 3 if pitch is None else int(pitch)
+    if pitch < out_w * 3 or dst.numel() < (N * out_h - 1) * pitch + out_w * 3:
+        raise _lib.ClslamError(f'resize_level_u8: {N} x {out_h} rows of {out_w} pixels at pitch {pitch} leave the {dst.numel()} bytes of dst')
+    if (w != out_w and plan_h is None) or (h != out_h and plan_v is None):
+        raise _lib.ClslamError(f'resize_level_u8: {h} x {w} -> {out_h} x {out_w} needs a tap plan per resized axis')
+    bh, kh, ksh = plan_h if w != out_w else (None, None, 0)
+    bv, kv, ksv = plan_v if h != out_h else (None, None, 0)
+    _lib.get_lib().call('clslam_resize_level_u8', _pa(src, torch.uint8), _pa(dst, torch.uint8), pitch, _pa(bh, torch.int32),
+                        _pa(kh, torch.int32), ksh, _pa(bv, torch.int32), _pa(kv, torch.int32), ksv, N, h, w, 3, int(out_h), int(out_w),
+                        _stream(src))
+
+
+def ring_gather(ring: torch.Tensor, slot_bytes: int, offsets, sizes, slots, rgb, aug) -> None:
+    """ring (capacity * slot_bytes,) uint8; offsets[level] bytes inside a slot, sizes[level] = (h, w); slots[frame] = the slot of that
+    frame; rgb / aug [frame * levels + level]: distinct contiguous float tensors of 3 * h * w values, both <- byte / 255."""
+    n_levels, n_frames = len(sizes), len(slots)
+    n_tab = n_frames * n_levels
+    if n_tab > _lib.STORE_MAX_PLANES or len(offsets) != n_levels or len(rgb) != n_tab or len(aug) != n_tab:
+        raise _lib.ClslamError(f'ring_gather: {n_frames} frames x {n_levels} levels, {len(offsets)} offsets, {len(rgb)} + {len(aug)} outputs')
+    desc = _lib.RingGatherDesc()
+    desc.n_frames, desc.n_levels, desc.slot_bytes = n_frames, n_levels, int(slot_bytes)
+    desc.capacity = ring.numel() // int(slot_bytes)
+    for li, (h, w) in enumerate(sizes):
+        desc.h[li], desc.w[li], desc.offset[li] = int(h), int(w), int(offsets[li])
+    for fi, slot in enumerate(slots):
+        desc.slot[fi] = int(slot)
+    for t in range(n_tab):
+        h, w = sizes[t % n_levels]
+        for out in (rgb[t], aug[t]):
+            if out.numel() != 3 * h * w:
+                raise _lib.ClslamError(f'ring_gather: entry {t} needs 3 x {h} x {w} values, got {tuple(out.shape)}')
+        desc.rgb[t], desc.aug[t] = _p(rgb[t]), _p(aug[t])
+    _lib.get_lib().call('clslam_ring_gather', C.byref(desc), _pa(ring, torch.uint8), _stream(ring))

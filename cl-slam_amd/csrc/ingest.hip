@@ -638,3 +638,165 @@ extern "C" int clslam_store_gather_jitter(const clslam_store_gather_desc* desc, 
                        slot_idx, (const clslam::JitterParams*)params, partial, n_images, row0);
     return clslam::check_launch("store_gather_jitter");
 }
+
+// =====================================================================================================================
+// Online ingest: the driver's own sample (slam/slam.py:141, datasets/kitti.py:231-317) from a ring of per-frame uint8 pyramids.
+// A frame's pyramid is built ONCE, one launch per level (clslam_resize_level_u8), into its ring slot; a sample is then one launch
+// (clslam_ring_gather) that turns the slots of its frames into the float planes of the sample dict.
+namespace clslam {
+
+// One pyramid level, both Pillow passes in one kernel.  A workgroup owns RL_TH output rows x RL_TW output columns.  It runs the
+// horizontal pass for the input rows its vertical taps reach and keeps the result in LDS AS BYTES (Pillow rounds and clips to
+// uint8 between the passes), RL_ROWS rows at a time; the vertical pass accumulates from LDS.  A tile whose vertical taps span
+// more than RL_ROWS input rows (ratios far above 2) takes several rounds: the int32 accumulator lives across them, and integer
+// sums do not depend on the order.  At the pyramid's 2:1 a tile reaches 15 * 2 + 13 = 43 rows: one round.
+// LDS per workgroup: RL_ROWS * RL_TW * 3 = 2304 bytes.  Arithmetic: resize_pass_u8_kernel's, tap for tap.
+constexpr int RL_TH = 16, RL_TW = 16, RL_ROWS = 48;
+
+// bh / kh == nullptr: no horizontal pass (in_w == ow); bv / kv == nullptr: no vertical pass (in_h == oh).
+__global__ __launch_bounds__(256) void resize_level_u8_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
+                                                              long long pitch, const int* __restrict__ bh, const int* __restrict__ kh,
+                                                              int ksh, const int* __restrict__ bv, const int* __restrict__ kv, int ksv,
+                                                              int in_h, int in_w, int oh, int ow) {
+    __shared__ unsigned char mid[RL_ROWS * RL_TW * 3];
+    const int tid = threadIdx.x, tx = tid % RL_TW, ty = tid / RL_TW;
+    const int x0 = blockIdx.x * RL_TW, y0 = blockIdx.y * RL_TH, b = blockIdx.z;
+    const int x = x0 + tx, y = y0 + ty;
+    const bool live = x < ow && y < oh;
+    const int ylast = min(y0 + RL_TH, oh) - 1;
+    // input rows of this tile (the plan's windows move monotonically with the output index)
+    const int row_lo = bv ? bv[2 * y0] : y0;
+    const int row_hi = bv ? bv[2 * ylast] + bv[2 * ylast + 1] : ylast + 1;
+    const int vfirst = live ? (bv ? bv[2 * y] : y) : 0, vn = live ? (bv ? bv[2 * y + 1] : 1) : 0;
+    const int* vk = (bv && live) ? kv + (size_t)y * ksv : nullptr;
+    const int cols = min(RL_TW, ow - x0);
+    const unsigned char* img = src + (size_t)b * in_h * in_w * 3;
+    int acc[3] = {1 << (RS_PRECISION_BITS - 1), 1 << (RS_PRECISION_BITS - 1), 1 << (RS_PRECISION_BITS - 1)};
+    for (int r0 = row_lo; r0 < row_hi; r0 += RL_ROWS) {
+        const int rows = min(RL_ROWS, row_hi - r0);
+        // horizontal pass: rows x cols intermediate pixels, column-fastest over the threads
+        for (int i = tid; i < rows * cols; i += 256) {
+            const int r = i / cols, c = i - r * cols;
+            const int ox = x0 + c;
+            const unsigned char* line = img + (size_t)(r0 + r) * in_w * 3;
+            unsigned char* m = mid + (r * RL_TW + c) * 3;
+            if (!bh) {
+                m[0] = line[ox * 3]; m[1] = line[ox * 3 + 1]; m[2] = line[ox * 3 + 2];
+                continue;
+            }
+            const int first = bh[2 * ox], n = bh[2 * ox + 1];
+            const int* k = kh + (size_t)ox * ksh;
+            const unsigned char* p = line + (size_t)first * 3;
+            int a0 = 1 << (RS_PRECISION_BITS - 1), a1 = a0, a2 = a0;
+            for (int t = 0; t < n; ++t) {
+                const int w = k[t];
+                a0 += (int)p[0] * w; a1 += (int)p[1] * w; a2 += (int)p[2] * w;
+                p += 3;
+            }
+            m[0] = (unsigned char)min(max(a0 >> RS_PRECISION_BITS, 0), 255);
+            m[1] = (unsigned char)min(max(a1 >> RS_PRECISION_BITS, 0), 255);
+            m[2] = (unsigned char)min(max(a2 >> RS_PRECISION_BITS, 0), 255);
+        }
+        __syncthreads();
+        // vertical pass: the taps of this thread's output row that fall into [r0, r0 + rows)
+        const int t_lo = max(0, r0 - vfirst), t_hi = min(vn, r0 + rows - vfirst);
+        for (int t = t_lo; t < t_hi; ++t) {
+            const unsigned char* m = mid + ((vfirst + t - r0) * RL_TW + tx) * 3;
+            if (!vk) {
+                acc[0] = m[0]; acc[1] = m[1]; acc[2] = m[2];
+                continue;
+            }
+            const int w = vk[t];
+            acc[0] += (int)m[0] * w; acc[1] += (int)m[1] * w; acc[2] += (int)m[2] * w;
+        }
+        __syncthreads();                     // the next round overwrites mid
+    }
+    if (!live) return;
+    unsigned char* o = dst + ((size_t)b * oh + y) * (size_t)pitch + (size_t)x * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (unsigned char)(bv ? min(max(acc[c] >> RS_PRECISION_BITS, 0), 255) : acc[c]);
+}
+
+// grid (blocks, frames, levels).  The slot keeps a level INTERLEAVED (h, w, 3), as the level kernel wrote it; every byte is read
+// once and goes to both planar destinations.  Four pixels per thread (three dwords in, three float4 per destination out) where
+// the level and both destinations are aligned for it, one pixel per thread otherwise.
+__global__ __launch_bounds__(256) void ring_gather_kernel(clslam_ring_gather_desc d, const unsigned char* __restrict__ ring) {
+    const int fi = blockIdx.y, li = blockIdx.z;
+    const int hw = d.h[li] * d.w[li];
+    if ((int)blockIdx.x * 256 >= hw) return;
+    const int table = fi * d.n_levels + li;
+    const unsigned char* __restrict__ bytes = ring + (size_t)d.slot[fi] * (size_t)d.slot_bytes + (size_t)d.offset[li];
+    float* __restrict__ rgb = d.rgb[table];
+    float* __restrict__ aug = d.aug[table];
+    const bool aligned = (hw & 3) == 0 && ((uintptr_t)bytes & 3) == 0 && ((uintptr_t)rgb & 15) == 0 && ((uintptr_t)aug & 15) == 0;
+    const int nvec = aligned ? hw >> 2 : 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) {
+        const unsigned* q = reinterpret_cast<const unsigned*>(bytes) + 3 * (size_t)i;
+        const unsigned q0 = q[0], q1 = q[1], q2 = q[2];            // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+        const float r0 = (float)(q0 & 255u) / 255.f, g0 = (float)((q0 >> 8) & 255u) / 255.f, b0 = (float)((q0 >> 16) & 255u) / 255.f;
+        const float r1 = (float)(q0 >> 24) / 255.f, g1 = (float)(q1 & 255u) / 255.f, b1 = (float)((q1 >> 8) & 255u) / 255.f;
+        const float r2 = (float)((q1 >> 16) & 255u) / 255.f, g2 = (float)(q1 >> 24) / 255.f, b2 = (float)(q2 & 255u) / 255.f;
+        const float r3 = (float)((q2 >> 8) & 255u) / 255.f, g3 = (float)((q2 >> 16) & 255u) / 255.f, b3 = (float)(q2 >> 24) / 255.f;
+        const float4 R = make_float4(r0, r1, r2, r3), G = make_float4(g0, g1, g2, g3), B = make_float4(b0, b1, b2, b3);
+        reinterpret_cast<float4*>(rgb)[i] = R;
+        reinterpret_cast<float4*>(rgb + hw)[i] = G;
+        reinterpret_cast<float4*>(rgb + 2 * hw)[i] = B;
+        reinterpret_cast<float4*>(aug)[i] = R;
+        reinterpret_cast<float4*>(aug + hw)[i] = G;
+        reinterpret_cast<float4*>(aug + 2 * hw)[i] = B;
+    }
+    for (int i = 4 * nvec + blockIdx.x * 256 + threadIdx.x; i < hw; i += gridDim.x * 256) {
+        const unsigned char* p = bytes + (size_t)i * 3;
+        const float r = (float)p[0] / 255.f, g = (float)p[1] / 255.f, b = (float)p[2] / 255.f;
+        rgb[i] = r; rgb[hw + i] = g; rgb[2 * hw + i] = b;
+        aug[i] = r; aug[hw + i] = g; aug[2 * hw + i] = b;
+    }
+}
+
+}  // namespace clslam
+
+extern "C" int clslam_resize_level_u8(const unsigned char* src, unsigned char* dst, long long dst_pitch, const int* bounds_h,
+                                      const int* coeffs_h, int ksize_h, const int* bounds_v, const int* coeffs_v, int ksize_v,
+                                      int batch, int in_h, int in_w, int ch, int out_h, int out_w, void* stream) {
+    CLSLAM_REQUIRE(batch >= 0 && in_h > 0 && in_w > 0 && out_h > 0 && out_w > 0, "resize_level_u8: bad geometry (%d images, %d x %d -> %d x %d)",
+                   batch, in_h, in_w, out_h, out_w);
+    CLSLAM_REQUIRE(ch == 3, "resize_level_u8: %d channels (interleaved RGB only)", ch);
+    if (batch == 0) return CLSLAM_OK;
+    CLSLAM_REQUIRE(src && dst, "resize_level_u8: null pointer");
+    CLSLAM_REQUIRE(dst_pitch >= (long long)out_w * 3, "resize_level_u8: a row pitch of %lld bytes is shorter than a row of %d pixels",
+                   dst_pitch, out_w);
+    CLSLAM_REQUIRE(in_w == out_w || (bounds_h && coeffs_h && ksize_h > 0), "resize_level_u8: width %d -> %d without a tap plan", in_w, out_w);
+    CLSLAM_REQUIRE(in_h == out_h || (bounds_v && coeffs_v && ksize_v > 0), "resize_level_u8: height %d -> %d without a tap plan", in_h, out_h);
+    CLSLAM_REQUIRE(batch <= 65535 && cdiv(out_h, RL_TH) <= 65535 && (size_t)batch * in_h * in_w < ((size_t)1 << 31) / 3 &&
+                       (size_t)batch * out_h * (size_t)dst_pitch < ((size_t)1 << 40),
+                   "resize_level_u8: image too large");
+    const bool hpass = in_w != out_w, vpass = in_h != out_h;
+    hipLaunchKernelGGL(resize_level_u8_kernel, dim3(cdiv(out_w, RL_TW), cdiv(out_h, RL_TH), batch), dim3(256), 0, (hipStream_t)stream, src,
+                       dst, dst_pitch, hpass ? bounds_h : nullptr, hpass ? coeffs_h : nullptr, ksize_h, vpass ? bounds_v : nullptr,
+                       vpass ? coeffs_v : nullptr, ksize_v, in_h, in_w, out_h, out_w);
+    return check_launch("resize_level_u8");
+}
+
+extern "C" int clslam_ring_gather(const clslam_ring_gather_desc* desc, const unsigned char* ring, void* stream) {
+    CLSLAM_REQUIRE(desc && ring, "ring_gather: null pointer");
+    CLSLAM_REQUIRE(desc->n_frames >= 1 && desc->n_levels >= 1 && desc->n_frames * desc->n_levels <= CLSLAM_STORE_MAX_PLANES,
+                   "ring_gather: %d frames x %d levels (at most %d planes)", desc->n_frames, desc->n_levels, CLSLAM_STORE_MAX_PLANES);
+    CLSLAM_REQUIRE(desc->capacity >= 1 && desc->slot_bytes > 0, "ring_gather: an empty ring");
+    int most = 1;
+    for (int li = 0; li < desc->n_levels; ++li) {
+        CLSLAM_REQUIRE(desc->h[li] > 0 && desc->w[li] > 0 && (size_t)desc->h[li] * desc->w[li] < ((size_t)1 << 29),
+                       "ring_gather: bad size of level %d", li);
+        CLSLAM_REQUIRE(desc->offset[li] >= 0 && desc->offset[li] + 3ll * desc->h[li] * desc->w[li] <= desc->slot_bytes,
+                       "ring_gather: level %d leaves the slot", li);
+        most = std::max(most, desc->h[li] * desc->w[li]);
+    }
+    for (int fi = 0; fi < desc->n_frames; ++fi)
+        CLSLAM_REQUIRE(desc->slot[fi] >= 0 && desc->slot[fi] < desc->capacity, "ring_gather: frame %d in slot %d of a ring of %d", fi,
+                       desc->slot[fi], desc->capacity);
+    for (int t = 0; t < desc->n_frames * desc->n_levels; ++t)
+        CLSLAM_REQUIRE(desc->rgb[t] && desc->aug[t] && desc->rgb[t] != desc->aug[t], "ring_gather: bad destination of table entry %d", t);
+    const int blocks = std::max(1, std::min(256, clslam::cdiv(most, 4 * 256)));
+    hipLaunchKernelGGL(clslam::ring_gather_kernel, dim3(blocks, desc->n_frames, desc->n_levels), dim3(256), 0, (hipStream_t)stream, *desc,
+                       ring);
+    return clslam::check_launch("ring_gather");
+}

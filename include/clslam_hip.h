@@ -43,9 +43,9 @@ extern "C" {
  * 104 = per-scale range forms of the four pyramid launches added; 105 = clslam_depth_metrics* added; 106 = clslam_pcl_* added;
  * 107 = the range forms of 104 and the unfused pyramid backward removed; 108 = clslam_store_* added (frame store);
  * 109 = the batched-copy and the fused reduction + Adam entry points removed (DESIGN.md "Retired step paths");
- * 110 = clslam_pose_pair_error, clslam_traj_metrics* added.
+ * 110 = clslam_pose_pair_error, clslam_traj_metrics* added; 111 = clslam_resize_level_u8, clslam_ring_gather added (online ingest).
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 110
+#define CLSLAM_ABI_VERSION 111
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -601,6 +601,38 @@ int clslam_pose_pair_error(const double* a, const double* b, int n, int a_invert
 int clslam_traj_metrics_scratch(int n);
 int clslam_traj_metrics(const double* pred, const double* gt, int n, int optimize_scale, double* out, double* segments,
                         double* dist, double* scratch, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Online ingest: the sample the driver takes from its DataLoader in front of every frame (slam/slam.py:141), assembled from a
+ * ring of per-frame uint8 pyramids in device memory.  A ring SLOT holds one frame: per level an INTERLEAVED (h, w, 3) uint8 image
+ * at a fixed byte offset.
+ *
+ * clslam_resize_level_u8 replaces one Resize(LANCZOS) of datasets/kitti.py:258 / datasets/utils.py:163 (one pyramid level from the
+ * raw frame or from the level above) in ONE launch: src (batch, in_h, in_w, 3) contiguous -> dst (batch, out_h, out_w, 3) with
+ * dst_pitch bytes between rows (>= out_w * 3; the bytes between two rows are not touched; image n starts at n * out_h *
+ * dst_pitch).  Both Pillow passes run in the kernel, the horizontal one into a uint8 tile in LDS: BITWISE what
+ * clslam_resize_pass_u8 (axis 1) followed by clslam_resize_pass_u8 (axis 0) writes.  bounds_* / coeffs_* / ksize_*: the device
+ * copies of clslam_lanczos_plan(in_w, out_w) and (in_h, out_h); an axis whose size does not change takes no pass and its tables
+ * are not read (may be NULL): in_w == out_w is the vertical pass alone, in_h == out_h the horizontal one, both a copy.  ch must
+ * be 3.
+ *
+ * clslam_ring_gather replaces the ToTensor of datasets/kitti.py:345-347 (datasets/utils.py:213-215) for the 2 * n_frames *
+ * n_levels image entries of one sample, in ONE launch: frame f lives in slot[f] (HOST values, each in [0, capacity)), level l at
+ * offset[l] bytes inside the slot with h[l] x w[l] pixels; rgb[f * n_levels + l] and aug[f * n_levels + l] (distinct, contiguous
+ * (3, h, w) float planes) both receive (float)byte / 255.f, clslam_u8_to_planar_f32's expression.                              */
+typedef struct clslam_ring_gather_desc {
+    float* rgb[CLSLAM_STORE_MAX_PLANES];
+    float* aug[CLSLAM_STORE_MAX_PLANES];
+    int64_t offset[CLSLAM_STORE_MAX_PLANES];                        /* by level */
+    int32_t h[CLSLAM_STORE_MAX_PLANES], w[CLSLAM_STORE_MAX_PLANES]; /* by level */
+    int32_t slot[CLSLAM_STORE_MAX_PLANES];                          /* by frame */
+    int32_t n_frames, n_levels, capacity;                           /* capacity: slots in the ring */
+    int64_t slot_bytes;
+} clslam_ring_gather_desc;
+int clslam_resize_level_u8(const unsigned char* src, unsigned char* dst, long long dst_pitch, const int* bounds_h,
+                           const int* coeffs_h, int ksize_h, const int* bounds_v, const int* coeffs_v, int ksize_v, int batch,
+                           int in_h, int in_w, int ch, int out_h, int out_w, void* stream);
+int clslam_ring_gather(const clslam_ring_gather_desc* desc, const unsigned char* ring, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,12 @@ colour jitter, per sample and frame) + concatenation with the online sample + ad
       path holds at `add` time, `get` is two launches over bytes in HBM, cat_dict fills row 0.  Reported warm (steady state) and
       for the first frames after a restart (store empty: every sample is a miss, decoded and packed).
     python tools/real_frame.py [frames=40] [K=4] [modes: comma-separated substrings, default all]
+    python tools/real_frame.py [frames=40] [K=4] online
+The `online` mode times what stands in FRONT of all that, `online_data = next(self.online_dataloader_iter)` (slam.py:141), and the
+whole frame behind it (replay from the frame store, mode (c)), on one tree of KITTI-sized PNGs, three runs each:
+  (y) the parent's path: a dataset whose __getitem__ is datasets/kitti.py:231-317 (three PNGs, three LANCZOS chains, 24 ToTensor
+      planes, with Pillow) behind DataLoader(batch_size=1, num_workers=0), and
+  (t) clslam_hip.ingest.OnlineSampleBuilder installed on the same dataset object: its first frame and its steady state.
 KITTI-sized PNGs (376x1241) are written to a temporary directory first.  Measurement tool (no parity claim: the parity of (b)
 is tests/test_replay_ingest.py); the host-side jitter in (a) is a plain torch restatement good enough for timing."""
 import pickle
@@ -124,13 +130,19 @@ pick = np.random.default_rng(1)
 
 
 DETAIL = {}
+ONLINE_SOURCE = None          # `online` mode: where the frame's online sample comes from
+NEXT_MS = []
 
 
 def frame(mode, detail=False):
     sync = torch.cuda.synchronize if detail else (lambda: None)
     tick = time.perf_counter
     ta = tick()
-    online = dict(online_host)
+    if ONLINE_SOURCE is None:
+        online = dict(online_host)
+    else:
+        online = next(ONLINE_SOURCE)                                                                # slam.py:141
+        NEXT_MS.append((tick() - ta) * 1e3)
     feat = p.models['depth_encoder'](online['rgb', 0, 0].to(dev))[4].mean(-1).mean(-1).cpu()      # slam.py:143-147
     sync()
     fns = [files[i] for i in pick.choice(STORE, K, replace=False)]
@@ -160,6 +172,104 @@ def frame(mode, detail=False):
             DETAIL[name] = DETAIL.get(name, 0.0) + v
     return t1 - t0
 
+
+class KittiShaped:
+    """datasets/kitti.py:231-317 with Pillow (torchvision's Resize(LANCZOS) / ToTensor of PIL images are these calls), as far as the
+    driver's configuration uses it; the camera matrices are synth's, so that its samples join the stored ones"""
+
+    def __init__(self, root, n_files):
+        self.frame_ids, self.scales, self.height, self.width = sorted(FRAMES), SCALES, H, W
+        self.do_augmentation, self.views, self.with_depth, self.with_mask, self.include_poses = False, ('left',), False, False, True
+        self.left_img_filenames = []
+        for i in range(n_files):
+            img = (rng.random((RAW_H // 8, RAW_W // 8, 3)) * 255).astype(np.uint8)
+            self.left_img_filenames.append(root / f'{i:06}.png')
+            Image.fromarray(img).resize((RAW_W, RAW_H), Image.BICUBIC).save(self.left_img_filenames[-1])
+        self.camera_matrix = np.eye(4, dtype=np.float32)
+        self.relative_distances = [0.] + [0.8] * (n_files - 1)
+        self.global_poses = [np.eye(4, dtype=np.float32)] * n_files
+        self.relative_poses = np.stack(self.global_poses)
+
+    def __len__(self):
+        return len(self.left_img_filenames) - 2
+
+    def _scale_camera_matrix(self, camera_matrix, scale):
+        k, kinv = synth.camera_matrices(H, W, scale)
+        return np.asarray(k), np.asarray(kinv, dtype=np.float32)
+
+    def _pre_getitem(self, index):
+        if index < 0 or index >= len(self):
+            raise IndexError()
+        return self.left_img_filenames, [], index + 1, False, False
+
+    def __getitem__(self, index):
+        names, _, index, _, _ = self._pre_getitem(index)
+        item, planes = {'index': index}, {}
+        for f in self.frame_ids:
+            rgb = Image.open(names[index + f]).convert('RGB')
+            for s in self.scales:
+                rgb = rgb.resize((W >> s, H >> s), Image.LANCZOS)
+                planes['rgb', f, s] = rgb
+        for s in range(len(self.scales)):
+            k, kinv = self._scale_camera_matrix(self.camera_matrix, s)
+            item['camera_matrix', s], item['inv_camera_matrix', s] = torch.from_numpy(k.copy()), torch.from_numpy(kinv.copy())
+        for f in self.frame_ids[1:]:
+            item['relative_distance', f] = self.relative_distances[index + f]
+        for f in self.frame_ids[1:]:
+            item['relative_pose', f] = torch.from_numpy(self.relative_poses[index + f][None].copy())
+            item['absolute_pose', f] = torch.from_numpy(self.global_poses[index + f][None].copy())
+        for kind in ('rgb', 'rgb_aug'):
+            for (_, f, s), img in planes.items():
+                item[kind, f, s] = torch.from_numpy(np.asarray(img).transpose(2, 0, 1).copy()).to(torch.float32).div(255)
+        return item
+
+
+def online_mode():
+    global ONLINE_SOURCE
+    from types import SimpleNamespace
+    from torch.utils.data import DataLoader
+    tree = work / 'image_2'
+    tree.mkdir()
+    ds = KittiShaped(tree, N + 3)
+    print(f'online sample + real frame @{H}x{W} ({RAW_H}x{RAW_W} PNGs), K = {K} replay samples from the frame store, 3 runs of 1 + {N} frames')
+    for _ in range(STORE):                                    # warm the step and the store up on the synthetic online sample
+        frame(STORE_MODE)
+    results = {}
+    for name in ('DataLoader(num_workers=0), host __getitem__', 'OnlineSampleBuilder'):
+        for run in range(3):
+            slam = SimpleNamespace(online_dataset=ds, online_dataloader_iter=iter(DataLoader(ds, batch_size=1, num_workers=0)))
+            builder = ingest.OnlineSampleBuilder(ds, dev).install(slam) if name == 'OnlineSampleBuilder' else None
+            ONLINE_SOURCE = slam.online_dataloader_iter
+            NEXT_MS.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            frame(STORE_MODE)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(N):
+                frame(STORE_MODE)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            results.setdefault(name, []).append((NEXT_MS[0], (t1 - t0) * 1e3, sum(NEXT_MS[1:]) / N, (t2 - t1) / N * 1e3))
+            if builder is not None:
+                builder.close()
+                ds.__class__ = KittiShaped                     # the next run starts from the dataset's own class again
+        ONLINE_SOURCE = None
+    for name, runs in results.items():
+        for label, col in (('first frame : next()', 0), ('first frame : whole frame', 1), ('steady state: next()', 2),
+                           ('steady state: whole frame', 3)):
+            v = [r[col] for r in runs]
+            print(f'  {name:44s} {label:26s}: {sorted(v)[1]:8.2f} ms  (3 runs: {min(v):.2f} .. {max(v):.2f})')
+    # the share of the one new PNG per frame: its decode alone, on this host thread
+    t0 = time.perf_counter()
+    for fn in ds.left_img_filenames[:10]:
+        np.asarray(Image.open(fn).convert('RGB'))
+    print(f'  decode of one {RAW_H}x{RAW_W} PNG, one thread: {(time.perf_counter() - t0) / 10 * 1e3:.2f} ms')
+
+
+if ONLY == ['online']:
+    online_mode()
+    sys.exit(0)
 
 print(f'real frame @{H}x{W}, K = {K} replay samples from a store of {STORE} ({RAW_H}x{RAW_W} PNGs), {N} frames per mode')
 for mode in ('reference get (host)', 'gpu ingest, PNGs decoded in one thread', 'gpu ingest', 'gpu ingest, decoded frames cached',
