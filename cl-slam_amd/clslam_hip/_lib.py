@@ -123,6 +123,12 @@ _SIGNATURES = {
     'clslam_disp_mean_chunks': [],
     'clslam_disp_mean': [fptr, fptr, i32, i32, C.c_void_p],
     'clslam_loss_finalize': [C.POINTER(LossDesc), C.c_void_p],
+    'clslam_pair_loss': [fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_float, C.c_float, C.c_void_p],
+    'clslam_pair_loss_rng': [fptr, fptr, fptr, fptr, fptr, C.c_uint64, C.c_uint64, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_float,
+                             C.c_float, C.c_void_p],
+    'clslam_pair_loss_scratch': [i32],
+    'clslam_pair_loss_finalize': [fptr, i32, fptr, fptr, fptr, fptr, fptr, fptr, i32, i32, fptr, fptr, i32, i32, i32, C.c_float,
+                                  C.c_float, C.c_void_p],
     'clslam_photo_grad': [fptr, fptr, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
     'clslam_mbv3_stem': [fptr, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
     'clslam_dwconv': [fptr, fptr, fptr, fptr, fptr, i32, i32, i32, i32, i32, i32, i32, C.c_void_p],
@@ -175,7 +181,7 @@ _SIGNATURES = {
     'clslam_traj_metrics': [fptr, fptr, i32, i32, fptr, fptr, fptr, fptr, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
-ABI_VERSION = 111          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
+ABI_VERSION = 112          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32]}      # return size_t
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}

@@ -1347,6 +1347,89 @@ class Engine:
         self._pose_decoder(st, feats[4])
         return st.pose
 
+    def run_pair(self, image_0: torch.Tensor, image_1: torch.Tensor, *, want_loss: bool, K: Optional[torch.Tensor] = None,
+                 inv_K: Optional[torch.Tensor] = None, relative_distance: Optional[torch.Tensor] = None,
+                 noise: Optional[torch.Tensor] = None, sample_w: Optional[torch.Tensor] = None,
+                 smooth_w: Optional[torch.Tensor] = None) -> SimpleNamespace:
+        """predict_from_images (dpp.py:556-626): ONE depth-network pass over the 2N stacked frames on the caller's stream, the
+        pose network over cat(image_0, image_1) on the side stream (the chip shares forward() gives the two encoders of N
+        samples), then -- want_loss -- the fused scale-0 pair loss with image_1 as target and image_0 as source.
+        -> disp (2N,1,H,W) (image_0's first), pose (N,12), T (2,N,4,4) = [cam_T_cam(0,-1) (inverted), the plain transformation],
+        losses (7,) or None (ops.pair_loss_finalize's order).  Every returned tensor is a fresh allocation.
+        noise: (N,1,H,W), already x 1e-5 (parity runs); None draws it in the kernel from the engine's draw counter."""
+        self.pack_if_needed()
+        self._conv_workspace()
+        self.wait_training()
+        a, b = self._img(image_0.to(self.device)), self._img(image_1.to(self.device))
+        n = a.shape[0] if a.dim() == 4 else -1
+        H, W, dev = self.H, self.W, self.device
+        for name, t in (('image_0', a), ('image_1', b)):
+            if tuple(t.shape) != (n, 3, H, W):
+                raise ClslamError(f'predict_from_images: {name} must be (N, 3, {H}, {W}) with equal N, got {tuple(t.shape)}')
+        if want_loss:
+            if K is None or inv_K is None or sample_w is None:
+                raise ClslamError('predict_from_images: the loss needs camera_matrix, inv_camera_matrix and sample weights')
+            K, inv_K = self._mat(K.to(dev)), self._mat(inv_K.to(dev))
+            for name, t in (('camera_matrix', K), ('inv_camera_matrix', inv_K)):
+                if tuple(t.shape) != (n, 4, 4):
+                    raise ClslamError(f'predict_from_images: {name} must be ({n}, 4, 4), got {tuple(t.shape)}')
+            if noise is not None and tuple(noise.shape) != (n, 1, H, W):
+                raise ClslamError(f'predict_from_images: tie-break noise must be ({n}, 1, {H}, {W}), got {tuple(noise.shape)}')
+            if self.vel_scale > 0 and (relative_distance is None or relative_distance.numel() != n):
+                raise ClslamError(f'predict_from_images: relative_distance must hold {n} values')
+        key = ('pair', n)
+        st = self._ws.get(key)
+        if st is None:
+            E = lambda *s: torch.empty(*s, device=dev)  # noqa: E731
+            st = SimpleNamespace(denc=self._enc_bufs(2 * n), penc=self._enc_bufs(n), dec=self._depth_dec_bufs(2 * n),
+                                 pad=E(2 * n, 12), eye=torch.eye(4, device=dev).repeat(n, 1, 1), P=E(2, n, 3, 4),
+                                 nblk=ops.automask_blocks(H, W), scratch=E(ops.pair_loss_scratch(n)))
+            st.partial = E(n, st.nblk)
+            self._pose_dec_bufs(n, st)
+            self._ws[key] = st
+        main = torch.cuda.current_stream(dev) if dev.type == 'cuda' else None
+        side = self._side_streams()[0] if main is not None else None
+        self._cu_dec = self.cu_limit(n, 'decoders')
+        cu_pose, cu_depth = self.cu_limit(n, 'enc_pose'), self.cu_limit(n, 'enc_depth')
+
+        def pose_net():
+            f4 = self._encoder(self.enc['pose_encoder'], st.penc, n, [(a, b, 0, n)], cu_limit=cu_pose)[4]
+            self._pose_decoder(st, f4)
+
+        if side is not None:
+            side.wait_stream(main)
+            with self._on(side):
+                pose_net()
+        feats = self._encoder(self.enc['depth_encoder'], st.denc, 2 * n, [(a, None, 0, n), (b, None, n, n)], cu_limit=cu_depth)
+        keep, self._main = self._main, None          # a plain chain on the caller's stream (run_depth_decoder)
+        try:
+            self._depth_decoder(st.dec, feats)
+        finally:
+            self._main = keep
+        if side is not None:
+            main.wait_stream(side)
+        else:
+            pose_net()
+        # frame idx 0 of pose_to_proj is the inverted transform cam_T_cam(0,-1) the view synthesis needs (dpp.py:609-611), idx 1
+        # the plain one predict_from_images returns (dpp.py:593-595): the same six pose numbers in both halves
+        st.pad[:n].copy_(st.pose)
+        st.pad[n:].copy_(st.pose)
+        T = torch.empty(2, n, 4, 4, device=dev)
+        ops.pose_to_proj(st.pad, K if want_loss else st.eye, T, st.P)
+        out = SimpleNamespace(disp=st.dec.disp[0].unsqueeze(1).clone(), pose=st.pose.clone(), T=T, losses=None)
+        if want_loss:
+            disp1 = st.dec.disp[0][n:]
+            if noise is not None:
+                ops.pair_loss(disp1, a, b, inv_K, st.P[0], self._img(noise.to(dev)), st.partial, self.min_depth, self.max_depth)
+            else:
+                seed, offset = self._next_noise_draw()
+                ops.pair_loss_rng(disp1, a, b, inv_K, st.P[0], seed, offset, st.partial, self.min_depth, self.max_depth)
+            dist = (relative_distance.to(dev, torch.float64).reshape(-1).contiguous() if self.vel_scale > 0 else None)
+            out.losses = torch.empty(7, device=dev)
+            ops.pair_loss_finalize(st.partial, disp1, b, st.pose, dist, sample_w, smooth_w, self.smooth_intended, st.scratch,
+                                   out.losses, self.smooth_scale, self.vel_scale)
+        return out
+
     def _nhwc(self, f: torch.Tensor) -> torch.Tensor:
         """(N,C,h,w) feature -> NHWC fp32 storage on the device (a view when it already is one: run_encoder's outputs are)"""
         f = f.to(self.device, torch.float32)

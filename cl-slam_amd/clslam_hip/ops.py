@@ -593,6 +593,37 @@ def tie_break_noise(out, seed, offset):
     return out
 
 
+def pair_loss(disp, src, target, inv_k, proj, noise, partial, min_depth, max_depth, depth=None, sel=None, maps=None):
+    """Fused single-source view synthesis + photometric automask at scale 0: disp (B,H,W), src / target (B,3,H,W),
+    proj (B,3,4), noise (B,1,H,W) already x 1e-5 or None -> partial (B, automask_blocks(H, W)); depth (B,H,W), sel (B,H,W) u8
+    and maps (2,B,H,W) are written only when given."""
+    B, H, W = disp.shape
+    _lib.get_lib().call('clslam_pair_loss', _p(disp), _p(src), _p(target), _p(inv_k), _p(proj), _p(noise), _p(partial), _p(depth),
+                        _pa(sel, torch.uint8), _p(maps), B, H, W, _nd(min_depth), _nd(max_depth), _stream(partial))
+
+
+def pair_loss_rng(disp, src, target, inv_k, proj, seed, offset, partial, min_depth, max_depth, depth=None, sel=None, maps=None):
+    """pair_loss with the noise drawn in the kernel: the first value of element b * H * W + pixel of tie_break_noise(seed, offset)"""
+    if not seed:
+        raise _lib.ClslamError('pair_loss_rng: seed must be non-zero')
+    B, H, W = disp.shape
+    _lib.get_lib().call('clslam_pair_loss_rng', _p(disp), _p(src), _p(target), _p(inv_k), _p(proj), int(seed), int(offset), _p(partial),
+                        _p(depth), _pa(sel, torch.uint8), _p(maps), B, H, W, _nd(min_depth), _nd(max_depth), _stream(partial))
+
+
+def pair_loss_scratch(batch: int) -> int:
+    return _query('clslam_pair_loss_scratch', batch)
+
+
+def pair_loss_finalize(partial, disp, rgb0, pose, dist, sample_w, smooth_w, intended, scratch, losses, smooth_scale, vel_scale):
+    """losses (7) = reprojection, smooth, reg, depth_loss/scale_0, depth_loss (= that / 4), velocity, loss"""
+    B, H, W = disp.shape
+    n_smooth = 0 if (smooth_w is None or intended) else int(smooth_w.numel())
+    _lib.get_lib().call('clslam_pair_loss_finalize', _p(partial), partial.shape[1], _p(disp), _p(rgb0), _p(pose),
+                        _pa(dist, torch.float64), _p(sample_w), _p(smooth_w) if n_smooth else None, n_smooth, 1 if intended else 0,
+                        _p(scratch), _p(losses), B, H, W, float(smooth_scale), float(vel_scale or 0.0), _stream(losses))
+
+
 def smooth_intended_chunks() -> int:
     return _query('clslam_smooth_intended_chunks')
 

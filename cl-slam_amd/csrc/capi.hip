@@ -152,7 +152,8 @@ extern "C" int clslam_handoff_wait(void* event, void* producer_stream, void* con
 // 108: clslam_store_pack / clslam_store_gather_jitter added (frame store of the replay ingest)
 // 109: the batched-copy and the fused reduction + Adam entry points removed (the captured training step went with them)
 // 110: clslam_pose_pair_error, clslam_traj_metrics* (additive)
-extern "C" int clslam_version(void) { return 111; }
+// 112: clslam_pair_loss* (additive)
+extern "C" int clslam_version(void) { return 112; }
 // identity of the kernel sources this library was LINKED from (csrc/build.py passes it when it compiles this file, which it
 // does whenever any object is rebuilt): read from the loaded library, not from a file beside it
 #ifndef CLSLAM_BUILD_ID

@@ -194,6 +194,160 @@ __global__ __launch_bounds__(256) void photo_automask_kernel(const float* __rest
     if (threadIdx.x == 0) partial_all[((size_t)sc * B + b) * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
+// (1 - SSIM) / 2 and L1 of ONE pixel (ly, lx) of a staged tile for a PAIR of predicted images against the target: cm / l1
+// accumulate per image sum_c clamp((1 - SSIM_c) / 2, 0, 1) and sum_c |t - p|; kc (TRAIN) the 9 SSIM coefficients.  The map of
+// image j is (0.85 / 3) cm[j] + (0.15 / 3) l1[j].  This is the per-pixel body of photo_automask_kernel above, statement for
+// statement, as a function: calling it from that kernel instead changed the instruction schedule of its training variant, and
+// nothing the training step runs is to move with this feature.  tests/test_pair_loss_kernel.py holds the two to the same bits
+// (the block sums of both kernels on the same pair of images).
+template <bool TRAIN>
+__device__ __forceinline__ void photo_pair_px(const float (&tl)[3][PA_PH * PA_PW], const f32x2 (&tw)[3][PA_PH * PA_PW], int ly, int lx,
+                                              f32x2& cm, f32x2& l1, f32x2 (&kc)[9]) {
+    const float C1 = 0.0001f, C2 = 0.0009f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float tv[9];
+        float sy = 0.f, syy = 0.f;
+        f32x2 sx = {0.f, 0.f}, sxx = {0.f, 0.f}, sxy = {0.f, 0.f}, xc = {0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int e = (ly + k / 3) * PA_PW + lx + k % 3;
+            tv[k] = tl[c][e];
+            sy += tv[k]; syy += tv[k] * tv[k];
+            const f32x2 xv = tw[c][e];
+            if (k == 4) xc = xv;
+            sx += xv; sxx += xv * xv; sxy += xv * tv[k];
+        }
+        const float mu_y = div9(sy);
+        const float sig_y = div9(syy) - mu_y * mu_y;
+        const f32x2 mu_x = div9(sx);
+        const f32x2 sig_x = div9(sxx) - mu_x * mu_x, sig_xy = div9(sxy) - mu_x * mu_y;
+        const f32x2 n1 = 2.f * mu_x * mu_y + C1, n2 = 2.f * sig_xy + C2;
+        const f32x2 d1 = mu_x * mu_x + mu_y * mu_y + C1, d2 = sig_x + sig_y + C2;
+        const f32x2 dd = d1 * d2;
+        f32x2 inv_d;
+        inv_d.x = fast_rcp(dd.x); inv_d.y = fast_rcp(dd.y);
+        const f32x2 S = (n1 * n2) * inv_d;
+        const f32x2 raw = (1.f - S) * 0.5f;
+        cm += pk_min(pk_max(raw, 0.f), 1.f);
+        l1 += pk_abs(tv[4] - xc);
+        if constexpr (TRAIN) {
+            f32x2 kf;
+            kf.x = (raw.x >= 0.f && raw.x <= 1.f) ? (0.85f / 3.f) * (-0.5f) / 9.f : 0.f;
+            kf.y = (raw.y >= 0.f && raw.y <= 1.f) ? (0.85f / 3.f) * (-0.5f) / 9.f : 0.f;
+            kc[c * 3 + 0] = kf * inv_d * (2.f * mu_y * (n2 - n1) - S * (2.f * mu_x * (d2 - d1)));
+            kc[c * 3 + 1] = kf * inv_d * (-2.f * S * d1);
+            kc[c * 3 + 2] = kf * inv_d * (2.f * n1);
+        }
+    }
+}
+
+// Fused single-source view synthesis + photometric automask at scale 0, forward only (predict_from_images, dpp.py:602-620
+// with scales = (0,): _reconstruct_images of frame -1 and the scale-0 iteration of _compute_loss up to to_optimize).
+// A block owns the same 8 x 64 tile + 1-pixel halo as photo_automask_kernel, one sample per blockIdx.y.  Staging a halo
+// element does the whole view synthesis of that pixel: disparity -> depth -> back-projection -> projection -> the
+// grid_sample(border, align_corners=True) read of the source frame (the functions warp_fwd_kernel uses, the same
+// expressions in the same order, at the pixel the reflection padding of the SSIM block maps the element to -- the padding
+// acts on the IMAGE being compared, so a halo element outside the image is the warped image at the reflected pixel).  The
+// warped tile lives in LDS only, paired with the source frame itself (the identity candidate): the pair goes through
+// photo_pair_px exactly like the two reprojections of photo_automask_kernel.  3 x 660 x (4 + 8) + 16 = 23 776 bytes of
+// LDS per block.  Stored: partial[b][blk] = block sum of min(identity + noise, reprojection); and, only where the
+// pointers are non-null (tests, inspection), depth (B,H,W), sel (B,H,W) u8 (0: identity, 1: reprojection; the lower index
+// wins a tie) and maps (2,B,H,W) = [identity map without noise, reprojection map].
+// Noise: noise (B,1,H,W), already scaled by 1e-5, or (seed != 0) the FIRST value of tie_break_pair(seed, offset, e) with
+// element e = b * H * W + pixel -- element e of what clslam_tie_break_noise writes, out[2 * e].
+__global__ __launch_bounds__(256) void pair_loss_kernel(const float* __restrict__ disp, const float* __restrict__ src,
+                                                        const float* __restrict__ target, const float* __restrict__ Kinv,
+                                                        const float* __restrict__ P, const float* __restrict__ noise,
+                                                        float* __restrict__ partial, float* __restrict__ depth_out,
+                                                        unsigned char* __restrict__ sel_out, float* __restrict__ maps_out, int B,
+                                                        int H, int W, float da, float db, int dmode, int tilesX,
+                                                        unsigned long long seed, unsigned long long rng_offset) {
+    __shared__ float tl[3][PA_PH * PA_PW];   // target
+    __shared__ f32x2 tw[3][PA_PH * PA_PW];   // (source warped into the target view, source as it is)
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const unsigned HW = (unsigned)(H * W);
+    const int ty = blockIdx.x / tilesX, tx = blockIdx.x - ty * tilesX;
+    const int y0 = ty * PA_TH, x0 = tx * PA_TW;
+    const float* dsp = disp + (size_t)b * HW;
+    const float* tgt = target + (size_t)b * 3 * HW;
+    const float* sp = src + (size_t)b * 3 * HW;
+    const float* Ki = Kinv + (size_t)b * 16;
+    const float* Pm = P + (size_t)b * 12;
+    for (int e = threadIdx.x; e < PA_PH * PA_PW; e += 256) {
+        const int r = e / PA_PW, c = e - r * PA_PW;
+        const int py = y0 - 1 + r, px = x0 - 1 + c;
+        // reflection padding; tiles overhanging the image clamp (those pixels are never consumed)
+        const int yy = min(max(refl(py, H), 0), H - 1), xx = min(max(refl(px, W), 0), W - 1);
+        const unsigned o = (unsigned)(yy * W + xx);
+        // F.interpolate to (H, W) is the identity at scale 0 (dpp.py:989): the disparity of the pixel itself
+        const float dep = disp_to_depth_dev(dsp[o], da, db, dmode);
+        if (depth_out && r >= 1 && r <= PA_TH && c >= 1 && c <= PA_TW && py < H && px < W) (depth_out + (size_t)b * HW)[o] = dep;
+        float X[3], cam[3];
+        backproject_px(Ki, (float)xx, (float)yy, dep, cam, X);
+        float u, v, den;
+        project_px(Pm, X, u, v, den);
+        const Sample s = sample_coords(u, v, H, W);
+        // the bilinear read of warp_fwd_kernel: clamped tap addresses, out-of-image taps skipped
+        const float wx1 = s.ix - (float)s.x0, wy1 = s.iy - (float)s.y0;
+        const float wx0 = (float)(s.x0 + 1) - s.ix, wy0 = (float)(s.y0 + 1) - s.iy;
+        const bool x1ok = s.x0 + 1 < W, y1ok = s.y0 + 1 < H;
+        const float w00 = wx0 * wy0, w10 = wx1 * wy0, w01 = wx0 * wy1, w11 = wx1 * wy1;
+        const unsigned o00 = (unsigned)(s.y0 * W + s.x0);
+        const unsigned o10 = o00 + (x1ok ? 1u : 0u);
+        const unsigned o01 = o00 + (y1ok ? (unsigned)W : 0u);
+        const unsigned o11 = o01 + (x1ok ? 1u : 0u);
+#pragma unroll
+        for (int c3 = 0; c3 < 3; ++c3) {
+            const float* pl = sp + (size_t)c3 * HW;
+            const float nw = pl[o00], ne = pl[o10], sw = pl[o01], se = pl[o11];
+            f32x2 pv;
+            pv.x = nw * w00;
+            if (x1ok) pv.x += ne * w10;
+            if (y1ok) pv.x += sw * w01;
+            if (x1ok && y1ok) pv.x += se * w11;
+            pv.y = pl[o];
+            tl[c3][e] = (tgt + (size_t)c3 * HW)[o];
+            tw[c3][e] = pv;
+        }
+    }
+    __syncthreads();
+    float sum = 0.f;
+#pragma unroll 1
+    for (int it = 0; it < (PA_TH * PA_TW) / 256; ++it) {
+        const int lp = threadIdx.x + it * 256;
+        const int ly = lp / PA_TW, lx = lp - ly * PA_TW;
+        const int y = y0 + ly, x = x0 + lx;
+        if (y >= H || x >= W) continue;
+        const unsigned p = (unsigned)(y * W + x);
+        f32x2 cm = {0.f, 0.f}, l1 = {0.f, 0.f};
+        f32x2 kc[9];
+        photo_pair_px<false>(tl, tw, ly, lx, cm, l1, kc);
+        const float rp = (0.85f / 3.f) * cm.x + (0.15f / 3.f) * l1.x;
+        const float idm = (0.85f / 3.f) * cm.y + (0.15f / 3.f) * l1.y;
+        float c0 = idm;
+        if (noise) c0 += noise[(size_t)b * HW + p];
+        else if (seed) {
+            float z0, z1;
+            tie_break_pair(seed, rng_offset, (size_t)b * HW + p, z0, z1);
+            c0 += z0;
+        }
+        const bool reproj = rp < c0;          // torch.min over [identity, reprojection]: the lower index wins a tie
+        const float m = reproj ? rp : c0;
+        if (sel_out) (sel_out + (size_t)b * HW)[p] = reproj ? 1 : 0;
+        if (maps_out) {
+            (maps_out + (size_t)b * HW)[p] = idm;
+            (maps_out + ((size_t)B + b) * HW)[p] = rp;
+        }
+        sum += m;
+    }
+    sum = wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
 // Loss backward v2 for the whole pyramid, LDS-tiled: a block owns an 8 x 64 pixel tile of one (scale,
 // sample); sel and the selected-frame coefficients of the tile + 1-pixel halo are staged once in LDS
 // (every neighbour a pixel needs -- incl. the reflection fold -- lies in its 3x3 neighbourhood), then each
@@ -1079,4 +1233,163 @@ extern "C" int clslam_smooth_intended_bwd(const float* const* disp, const float*
     hipLaunchKernelGGL(clslam::smooth_intended_bwd_kernel, dim3(clslam::cdiv(H * W, 256), batch, 4), dim3(256), 0, (hipStream_t)stream,
                        make_pyramid(disp, H, W), im, aux, sample_w, out, batch, smooth_scale);
     return check_launch("smooth_intended_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Pair loss (predict_from_images with return_loss, dpp.py:602-620): the loss dictionary of _compute_loss(scales=(0,)) from
+// the block sums of pair_loss_kernel.  One block.  losses[7] = reprojection_loss/scale_0, smooth_loss/scale_0,
+// reg_loss/scale_0, depth_loss/scale_0, depth_loss = depth_loss/scale_0 / 4 (dpp.py:1101 divides by len(self.scales), the
+// CONFIGURED scales, not by the one evaluated), velocity_loss, loss.
+// Smoothness of scale 0 as adapt() forms it: n_smooth > 0 -> the flattening behaviour of dpp.py:1148-1176 (term i = flat
+// element i of sample 0's gradient maps, the arithmetic of loss_finalize_kernel); si_partial != NULL -> the opt-in
+// per-sample term (the arithmetic of smooth_intended_finalize_kernel on the sums of smooth_intended_fwd_kernel).
+// Velocity: the term the loop of dpp.py:1125-1146 forms over frame_ids = (0, -1): frame 0 only, num_frames = 1.
+namespace clslam {
+
+__global__ __launch_bounds__(256) void pair_loss_finalize_kernel(const float* __restrict__ partial, int nblk,
+                                                                 const float* __restrict__ disp, const float* __restrict__ rgb0,
+                                                                 const float* __restrict__ means, const float* __restrict__ si_partial,
+                                                                 const float* __restrict__ pose, const double* __restrict__ dist,
+                                                                 const float* __restrict__ sample_w, const float* __restrict__ smooth_w,
+                                                                 int n_smooth, float* __restrict__ losses, int B, int H, int W,
+                                                                 float smooth_scale, float vel_scale) {
+    __shared__ float s_rl[FIN_MAXB], s_sm[FIN_MAXB], s_vel[FIN_MAXB], s_mean[FIN_MAXB];
+    const int tid = threadIdx.x;
+    const int hw = H * W;
+    const float invHW = 1.f / ((float)H * (float)W);
+    for (int b = tid; b < B; b += 256) {
+        float sum = 0.f;
+        for (int k = 0; k < DM_CHUNKS; ++k) sum += means[(size_t)b * DM_CHUNKS + k];
+        s_mean[b] = sum / (float)hw;
+    }
+    __syncthreads();
+    // 8 lanes per sample over the block sums (loss_finalize_kernel's order)
+    for (int b0 = 0; b0 < B; b0 += 32) {
+        const int b = b0 + (tid >> 3), kl = tid & 7;
+        const bool live = b < B;
+        float sum = 0.f;
+        if (live)
+            for (int k = kl; k < nblk; k += 8) sum += partial[(size_t)b * nblk + k];
+        sum += wave_shfl_xor(sum, 1);
+        sum += wave_shfl_xor(sum, 2);
+        sum += wave_shfl_xor(sum, 4);
+        if (live && kl == 0) s_rl[b] = (sum * invHW) * sample_w[b];
+    }
+    const int n_sm = si_partial ? B : n_smooth;
+    if (si_partial) {
+        for (int b = tid; b < B; b += 256) {
+            float T = 0.f;
+            for (int k = 0; k < SI_CHUNKS; ++k) T += si_partial[(size_t)b * SI_CHUNKS + k];
+            const float inv = 1.f / (s_mean[b] + 1e-7f);
+            s_sm[b] = (inv * T) * sample_w[b];
+        }
+    } else {
+        for (int i = tid; i < n_smooth; i += 256) {
+            const int h = H, w = W;
+            const int bx = i / (h * (w - 1)), rx = i % (h * (w - 1)), yx = rx / (w - 1), xx = rx % (w - 1);
+            const int by = i / ((h - 1) * w), ry = i % ((h - 1) * w), yy = ry / w, xy = ry % w;
+            const float* dxp = disp + (size_t)bx * h * w;
+            const float* dyp = disp + (size_t)by * h * w;
+            const float mx = s_mean[bx] + 1e-7f, my = s_mean[by] + 1e-7f;
+            const float ax = dxp[yx * w + xx] / mx, bxv = dxp[yx * w + xx + 1] / mx;
+            const float ay = dyp[yy * w + xy] / my, byv = dyp[(yy + 1) * w + xy] / my;
+            float gix = 0.f, giy = 0.f;
+            for (int c = 0; c < 3; ++c) {
+                const float* im_x = rgb0 + ((size_t)bx * 3 + c) * h * w;
+                const float* im_y = rgb0 + ((size_t)by * 3 + c) * h * w;
+                gix += fabsf(im_x[yx * w + xx] - im_x[yx * w + xx + 1]);
+                giy += fabsf(im_y[yy * w + xy] - im_y[(yy + 1) * w + xy]);
+            }
+            const float ex = expf(-(gix / 3.f)), ey = expf(-(giy / 3.f));
+            s_sm[i] = (fabsf(ax - bxv) * ex + fabsf(ay - byv) * ey) * smooth_w[i];
+        }
+    }
+    if (vel_scale > 0.f) {
+        for (int b = tid; b < B; b += 256) {
+            const float* t = pose + (size_t)b * 12 + 3;
+            const float nrm = sqrtf(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+            const float acc = (float)(0.0 + fabs((double)nrm - fabs(dist[b])));   // fp32 += fp64 (dpp.py:1142), / num_frames = 1
+            s_vel[b] = (vel_scale * acc) * sample_w[b];
+        }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    float rl = 0.f, sm = 0.f, vel = 0.f;
+    for (int b = 0; b < B; ++b) rl += s_rl[b];
+    for (int i = 0; i < n_sm; ++i) sm += s_sm[i];
+    const float reg = smooth_scale * sm;
+    const float loss0 = rl + reg;
+    float total = loss0 / 4.f;
+    losses[0] = rl; losses[1] = sm; losses[2] = reg; losses[3] = loss0; losses[4] = total;
+    if (vel_scale > 0.f) {
+        for (int b = 0; b < B; ++b) vel += s_vel[b];
+        total += vel;
+    }
+    losses[5] = vel;
+    losses[6] = total;
+}
+
+}  // namespace clslam
+
+static int pair_loss_launch(const float* disp, const float* src, const float* target, const float* inv_k, const float* proj,
+                            const float* noise, unsigned long long seed, unsigned long long offset, float* partial, float* depth,
+                            unsigned char* sel, float* maps, int batch, int H, int W, float min_depth, float max_depth,
+                            void* stream) {
+    CLSLAM_REQUIRE(disp && src && target && inv_k && proj && partial && H >= 2 && W >= 2, "pair_loss: bad args");
+    CLSLAM_REQUIRE(!(min_depth <= 0.f && max_depth > 0.f), "pair_loss: min_depth is None");
+    CLSLAM_REQUIRE((size_t)3 * H * W < ((size_t)1 << 31), "pair_loss: image too large for 32-bit indexing");
+    float a, b; int mode;
+    depth_mode(min_depth, max_depth, &a, &b, &mode);
+    if (!batch) return CLSLAM_OK;
+    const int tilesX = cdiv(W, PA_TW);
+    hipLaunchKernelGGL(pair_loss_kernel, dim3(clslam_automask_blocks(H, W), batch), dim3(256), 0, (hipStream_t)stream, disp, src,
+                       target, inv_k, proj, noise, partial, depth, sel, maps, batch, H, W, a, b, mode, tilesX, seed, offset);
+    return check_launch("pair_loss");
+}
+
+extern "C" int clslam_pair_loss(const float* disp, const float* src, const float* target, const float* inv_k, const float* proj,
+                                const float* noise, float* partial, float* depth, unsigned char* sel, float* maps, int batch,
+                                int H, int W, float min_depth, float max_depth, void* stream) {
+    return pair_loss_launch(disp, src, target, inv_k, proj, noise, 0ull, 0ull, partial, depth, sel, maps, batch, H, W, min_depth,
+                            max_depth, stream);
+}
+
+extern "C" int clslam_pair_loss_rng(const float* disp, const float* src, const float* target, const float* inv_k,
+                                    const float* proj, unsigned long long seed, unsigned long long offset, float* partial,
+                                    float* depth, unsigned char* sel, float* maps, int batch, int H, int W, float min_depth,
+                                    float max_depth, void* stream) {
+    CLSLAM_REQUIRE(seed != 0, "pair_loss_rng: seed must be non-zero");
+    return pair_loss_launch(disp, src, target, inv_k, proj, nullptr, seed, offset, partial, depth, sel, maps, batch, H, W,
+                            min_depth, max_depth, stream);
+}
+
+// floats of scratch clslam_pair_loss_finalize needs: the chunk sums of the disparity and of the per-sample smoothness
+extern "C" int clslam_pair_loss_scratch(int batch) { return batch * (DM_CHUNKS + clslam::SI_CHUNKS); }
+
+extern "C" int clslam_pair_loss_finalize(const float* partial, int nblk, const float* disp, const float* rgb0, const float* pose,
+                                         const double* dist, const float* sample_w, const float* smooth_w, int n_smooth,
+                                         int intended, float* scratch, float* losses, int batch, int H, int W,
+                                         float smooth_scale, float vel_scale, void* stream) {
+    CLSLAM_REQUIRE(partial && disp && rgb0 && pose && sample_w && scratch && losses && nblk > 0, "pair_loss_finalize: null");
+    CLSLAM_REQUIRE(batch >= 1 && batch <= FIN_MAXB && n_smooth >= 0 && n_smooth <= FIN_MAXB, "pair_loss_finalize: batch > %d", FIN_MAXB);
+    CLSLAM_REQUIRE(vel_scale <= 0.f || dist, "pair_loss_finalize: relative distance missing");
+    CLSLAM_REQUIRE(H >= 2 && W >= 2, "pair_loss_finalize: image too small");
+    if (intended) n_smooth = 0;
+    CLSLAM_REQUIRE(n_smooth == 0 || (smooth_w && n_smooth < W - 1), "pair_loss_finalize: reference smoothness layout needs batch < width - 1");
+    Pyramid pyr;
+    pyr.n = 1; pyr.disp[0] = disp; pyr.h[0] = H; pyr.w[0] = W;
+    for (int k = 1; k < 4; ++k) { pyr.disp[k] = nullptr; pyr.h[k] = pyr.w[k] = 0; }
+    float* means = scratch;
+    float* si_partial = intended ? scratch + (size_t)batch * DM_CHUNKS : nullptr;
+    hipLaunchKernelGGL(disp_mean_kernel, dim3(DM_CHUNKS, batch, 1), dim3(256), 0, (hipStream_t)stream, pyr, means, batch);
+    if (intended) {
+        clslam::SiPtrs im;
+        im.rgb0[0] = rgb0;
+        for (int k = 1; k < 4; ++k) im.rgb0[k] = nullptr;
+        hipLaunchKernelGGL(clslam::smooth_intended_fwd_kernel, dim3(clslam::SI_CHUNKS, batch, 1), dim3(256), 0, (hipStream_t)stream,
+                           pyr, im, si_partial, batch);
+    }
+    hipLaunchKernelGGL(clslam::pair_loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nblk, disp, rgb0, means,
+                       si_partial, pose, dist, sample_w, smooth_w, n_smooth, losses, batch, H, W, smooth_scale, vel_scale);
+    return check_launch("pair_loss_finalize");
 }

@@ -13,8 +13,8 @@ min_depth, max_depth, log_path``; the caller's input dict is moved to the device
 What is different by design: all arithmetic runs in ``clslam_hip.engine.Engine`` (no autograd, no
 torch.nn compute); there is NO CPU path -- constructing the predictor without a GPU / without
 libclslam_hip.so raises.  Provided from the evaluation side: ``compute_depth_error`` (dpp.py:344-468, the metrics on the device:
-clslam_hip/depth_eval.py) and ``predict_from_image`` (dpp.py:538-554).  Offline pre-training, the other evaluators and plotting
-(dpp.py:219-289, 321-342, 470-526, 556-626, 829-904, 1197-1267) are outside the accelerated path and not provided.
+clslam_hip/depth_eval.py), ``predict_from_image`` (dpp.py:538-554) and ``predict_from_images`` (dpp.py:556-626).  Offline
+pre-training and plotting (dpp.py:219-289, 829-904, 1197-1267) are outside the accelerated path and not provided.
 """
 import math
 import shutil
@@ -580,6 +580,76 @@ class DepthPosePrediction:
         if as_numpy:
             depth = depth.squeeze().cpu().detach().numpy()
         return depth
+
+    def predict_from_images(
+            self,
+            image_0: Tensor,
+            image_1: Tensor,
+            as_numpy: bool = True,
+            return_loss: bool = False,
+            camera_matrix: Optional[Tensor] = None,
+            inv_camera_matrix: Optional[Tensor] = None,
+            relative_distance: Optional[Tensor] = None,
+    ):
+        """Take two images as input and return depth for both and relative pose (dpp.py:556-626): depth_0, depth_1,
+        transformation (invert=False) and, with return_loss, the loss dict of the pair (image_0 = frame -1 is the source,
+        image_1 = frame 0 the target; _compute_loss(scales=(0,)), dpp.py:602-620) as numpy scalars.  One depth-network pass
+        over both frames, the pose network beside it, the loss in one fused kernel (Engine.run_pair).  self.frame_ids is not
+        touched.  Two things to know about the loss:
+          * depth_loss = depth_loss/scale_0 / 4: dpp.py:1101 divides by len(self.scales), the configured scales, although one
+            scale is evaluated.  Kept as the reference has it.
+          * velocity_loss_scaling > 0: the reference cannot return here (_compute_velocity_loss reads inputs['index'], which
+            this call never supplies: KeyError).  This class computes the term its loop over frame_ids = (0, -1) evidently
+            forms -- velocity_loss_scaling * | |translation(0,-1)| - |relative_distance| |, one frame, weighted like the other
+            terms -- reports it as 'velocity_loss' and adds it to 'loss'; 'depth_loss' stays the depth term alone.
+        Sample weights: ones(batch_size) / batch_size against the N pairs (dpp.py:1031-1032), so N is 1 or batch_size.
+        Tie-break noise: drawn on the device; a tensor set through set_tie_break_noise ({0: (N,1,H,W)} or the tensor) is used
+        instead (parity runs)."""
+        if not self.is_trained:
+            warnings.warn('The model has not been trained yet.', RuntimeWarning)
+        if len(image_0.shape) == 3:
+            image_0 = image_0.unsqueeze(dim=0)
+        if len(image_1.shape) == 3:
+            image_1 = image_1.unsqueeze(dim=0)
+        kw = {}
+        if return_loss:
+            if camera_matrix is None or inv_camera_matrix is None:
+                raise ValueError('predict_from_images(return_loss=True) needs camera_matrix and inv_camera_matrix')
+            vel = self.velocity_loss_scaling is not None and self.velocity_loss_scaling > 0
+            if vel and relative_distance is None:
+                raise ValueError('predict_from_images(return_loss=True) needs relative_distance when velocity_loss_scaling > 0')
+            sample_w, smooth_w = self._sample_weights(image_0.shape[0], None, local=True)
+            noise = self._injected_noise
+            if isinstance(noise, dict):
+                noise = noise[0]
+            if noise is not None:
+                noise = noise[:, :1].contiguous()
+            kw = dict(K=camera_matrix.reshape(-1, 4, 4), inv_K=inv_camera_matrix.reshape(-1, 4, 4),
+                      relative_distance=relative_distance if vel else None, noise=noise, sample_w=sample_w, smooth_w=smooth_w)
+        self._set_eval()
+        from depth_pose_prediction.utils import disp_to_depth
+        res = self.engine.run_pair(image_0, image_1, want_loss=return_loss, **kw)
+        n = res.pose.shape[0]
+        depth = disp_to_depth(res.disp, self.min_depth, self.max_depth)
+        depth_0, depth_1, transformation = depth[:n], depth[n:], res.T[1]
+        if as_numpy:
+            depth_0 = depth_0.squeeze().cpu().detach().numpy()
+            depth_1 = depth_1.squeeze().cpu().detach().numpy()
+            transformation = transformation.squeeze().cpu().detach().numpy()
+        if return_loss:
+            host = res.losses.cpu().numpy()          # the one read-back of the seven scalars
+            losses = {'reprojection_loss/scale_0': host[0], 'smooth_loss/scale_0': host[1], 'reg_loss/scale_0': host[2],
+                      'depth_loss/scale_0': host[3], 'depth_loss': host[4]}
+            if vel:
+                losses['velocity_loss'] = host[5]
+            losses['loss'] = host[6]
+            losses = {k: np.asarray(v) for k, v in losses.items()}
+            if np.isnan(losses['loss']):
+                for k, v in losses.items():
+                    print(k, v.item())
+                raise RuntimeError('NaN loss')
+            return depth_0, depth_1, transformation, losses
+        return depth_0, depth_1, transformation
 
     def compute_depth_error(self, median_scaling: bool = True, print_results: bool = True, data_loader=None) -> Dict[str, float]:
         """dpp.py:344-468 with the metrics on the device (ops.depth_metrics).  data_loader: any iterable of sample dicts holding

@@ -45,7 +45,7 @@ extern "C" {
  * 109 = the batched-copy and the fused reduction + Adam entry points removed (DESIGN.md "Retired step paths");
  * 110 = clslam_pose_pair_error, clslam_traj_metrics* added; 111 = clslam_resize_level_u8, clslam_ring_gather added (online ingest).
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 111
+#define CLSLAM_ABI_VERSION 112
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -304,6 +304,34 @@ typedef struct clslam_loss_desc {
     float smooth_scale, vel_scale;
 } clslam_loss_desc;
 int clslam_loss_finalize(const clslam_loss_desc* desc, void* stream);
+/* Pair loss: the photometric loss of ONE source frame at scale 0, forward only.  Replaces dpp.py:602-620
+ * (predict_from_images with return_loss: _reconstruct_images of frame -1, i.e. dpp.py:986-1017 with networks/layers.py:51-104
+ * and utils.py:120-142, and _compute_loss(scales=(0,)), dpp.py:1038-1113 with networks/layers.py:107-137).
+ * clslam_pair_loss: view synthesis, both photometric maps, the per-pixel minimum and its block sums in one kernel; the
+ * warped image stays on chip.  disp (B,H,W) = ('disp', 0) of the target; src / target (B,3,H,W); inv_k (B,4,4); proj (B,3,4)
+ * = (K * cam_T_cam(0,-1))[:3]; noise (B,1,H,W), already x 1e-5, or NULL; partial [B][clslam_automask_blocks(H, W)].
+ * Optional outputs, each may be NULL: depth (B,H,W); sel (B,H,W) u8, 0 = identity + noise, 1 = reprojection (a tie goes to
+ * 0); maps (2,B,H,W) = [identity map without noise, reprojection map].  With all three NULL only `partial` is written.
+ * clslam_pair_loss_rng draws the noise in the kernel: the FIRST value of element (b * H * W + pixel) of draw `offset`, key
+ * `seed` (non-zero), of the stream clslam_tie_break_noise writes -- out[2 * (b * H * W + pixel)] of that call.         */
+int clslam_pair_loss(const float* disp, const float* src, const float* target, const float* inv_k, const float* proj,
+                     const float* noise, float* partial, float* depth, unsigned char* sel, float* maps, int batch, int H,
+                     int W, float min_depth, float max_depth, void* stream);
+int clslam_pair_loss_rng(const float* disp, const float* src, const float* target, const float* inv_k, const float* proj,
+                         unsigned long long seed, unsigned long long offset, float* partial, float* depth, unsigned char* sel,
+                         float* maps, int batch, int H, int W, float min_depth, float max_depth, void* stream);
+/* losses[7] = reprojection_loss/scale_0, smooth_loss/scale_0, reg_loss/scale_0, depth_loss/scale_0, depth_loss
+ * (= depth_loss/scale_0 / 4: dpp.py:1101 divides by the configured scales), velocity_loss, loss.  rgb0 = the target frame;
+ * pose (B,12) rows [axis_angle, translation(0,-1), ...]; dist (B) float64 = ('relative_distance', 0), needed when
+ * vel_scale > 0: velocity_loss = vel_scale * | |translation| - |dist| | (the loop of dpp.py:1125-1146 over frame_ids (0,-1):
+ * one frame).  Smoothness as the step forms it at scale 0: intended = 0 -> the n_smooth flattened terms of
+ * dpp.py:1148-1176 weighted by smooth_w; intended != 0 -> the per-sample term of clslam_smooth_intended_*.
+ * scratch: clslam_pair_loss_scratch(batch) floats.                                                                    */
+int clslam_pair_loss_scratch(int batch);
+int clslam_pair_loss_finalize(const float* partial, int nblk, const float* disp, const float* rgb0, const float* pose,
+                              const double* dist, const float* sample_w, const float* smooth_w, int n_smooth, int intended,
+                              float* scratch, float* losses, int batch, int H, int W, float smooth_scale, float vel_scale,
+                              void* stream);
 /* dpred (2,B,3,H,W) = dL/d(warped images) of one scale.                                          */
 int clslam_photo_grad(const unsigned char* sel, const float* coef, const float* pred, const float* target,
                       const float* sample_w, float* dpred, int batch, int H, int W, void* stream);
