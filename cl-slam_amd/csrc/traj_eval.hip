@@ -26,12 +26,14 @@
 // launches agree bitwise.
 //
 // SCALE.  calc_error prints the scaling factor with all its digits (utils.py:362), so sum(X * Y) and sum(X ** 2) over the
-// flattened (n,3) translations are added in the order np.sum adds a contiguous array: numpy's pairwise summation -- a range of
-// more than 128 elements is split at half its length rounded down to a multiple of 8, a leaf of 8..128 elements runs eight
-// interleaved accumulators, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the remainder one by one; fewer than 8
-// elements are added one by one.  Every leaf starts at a multiple of 8: thread t of the leaf kernel descends the tree to the
-// leaf that holds element 8t and adds it if it starts there; one thread then walks the tree over the leaf sums with a stack in
-// LDS.  The products are rounded on their own (no fma), as numpy's are.
+// flattened (n,3) translations are added in the order np.sum adds a contiguous array.  numpy hands its add loop the array in
+// pieces of its buffer size, 8192 elements, and adds the sums of the pieces to the result one after the other, in order; only
+// INSIDE a piece is the summation pairwise -- a range of more than 128 elements is split at half its length rounded down to a
+// multiple of 8, a leaf of 8..128 elements runs eight interleaved accumulators, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) +
+// (r6 + r7)), then the remainder one by one; fewer than 8 elements are added one by one.  Every piece and every leaf starts at a
+// multiple of 8: thread t of the leaf kernel descends the tree of its piece to the leaf that holds element 8t and adds it if it
+// starts there; one thread then walks the tree of each piece over the leaf sums with a stack in LDS and adds the pieces up.
+// The products are rounded on their own (no fma), as numpy's are.
 #include "common.h"
 
 namespace clslam {
@@ -41,7 +43,8 @@ constexpr int kTePerThread = 4;                             // consecutive steps
 constexpr int kTeChunk = kTeThreads * kTePerThread;         // steps per scan block
 constexpr int kTeSums = 3;                                  // ATE term, RPE translation, RPE rotation
 constexpr int kTeLeaf = 128;                               // numpy's PW_BLOCKSIZE
-constexpr int kTeStack = 64;                                // nodes of the summation tree in flight (depth <= 16 for 3 * 2^20)
+constexpr int kTePiece = 8192;                              // numpy's default buffer size: one pairwise tree per piece
+constexpr int kTeStack = 64;                                // nodes of a summation tree in flight (depth <= 7 for a piece)
 constexpr int kTeSegCols = 6;                               // [first_frame, rot/length, trans/length, length, speed, last_frame]
 constexpr int kTeHeader = 8;                                // front of the scratch: [sum X.Y, sum X.X, scaling], the rest reserved
 
@@ -206,7 +209,7 @@ __global__ __launch_bounds__(256) void traj_scale_leaves_kernel(const double* __
     const int t = blockIdx.x * kTeThreads + threadIdx.x;
     const int e = 8 * t;
     if (e >= L) return;
-    int o = 0, n = L;
+    int o = e - e % kTePiece, n = min(kTePiece, L - o);                                 // the piece that holds element e
     while (n > kTeLeaf) {
         const int n2 = pairwise_left(n);
         if (e < o + n2) n = n2; else { o += n2; n -= n2; }
@@ -237,36 +240,42 @@ __global__ __launch_bounds__(256) void traj_scale_leaves_kernel(const double* __
     leaf[2 * (size_t)t + 1] = sxx;
 }
 
-// header = [sum X.Y, sum X.X, scaling]: one thread walks the tree, left child first, a node's sum = left + right
+// header = [sum X.Y, sum X.X, scaling]: one thread walks the tree of each piece, left child first, a node's sum = left + right,
+// and adds the sums of the pieces to 0 in order (np.add.reduce starts from the identity)
 __global__ __launch_bounds__(64) void traj_scale_tree_kernel(const double* __restrict__ leaf, int L, double* __restrict__ header) {
     __shared__ int node_o[kTeStack], node_n[kTeStack], node_seen[kTeStack];
     __shared__ double val_xy[kTeStack], val_xx[kTeStack];
     if (threadIdx.x != 0) return;
-    int sp = 1, vp = 0;
-    node_o[0] = 0; node_n[0] = L; node_seen[0] = 0;
-    while (sp > 0) {
-        const int o = node_o[sp - 1], n = node_n[sp - 1];
-        if (n <= kTeLeaf) {
-            val_xy[vp] = leaf[2 * (size_t)(o / 8)];
-            val_xx[vp] = leaf[2 * (size_t)(o / 8) + 1];
-            ++vp;
-            --sp;
-        } else if (!node_seen[sp - 1]) {
-            node_seen[sp - 1] = 1;
-            const int n2 = pairwise_left(n);
-            node_o[sp] = o + n2; node_n[sp] = n - n2; node_seen[sp] = 0;                // the right child waits below the left one
-            node_o[sp + 1] = o; node_n[sp + 1] = n2; node_seen[sp + 1] = 0;
-            sp += 2;
-        } else {
-            val_xy[vp - 2] = val_xy[vp - 2] + val_xy[vp - 1];
-            val_xx[vp - 2] = val_xx[vp - 2] + val_xx[vp - 1];
-            --vp;
-            --sp;
+    double sxy = 0.0, sxx = 0.0;
+    for (int piece = 0; piece < L; piece += kTePiece) {
+        int sp = 1, vp = 0;
+        node_o[0] = piece; node_n[0] = min(kTePiece, L - piece); node_seen[0] = 0;
+        while (sp > 0) {
+            const int o = node_o[sp - 1], n = node_n[sp - 1];
+            if (n <= kTeLeaf) {
+                val_xy[vp] = leaf[2 * (size_t)(o / 8)];
+                val_xx[vp] = leaf[2 * (size_t)(o / 8) + 1];
+                ++vp;
+                --sp;
+            } else if (!node_seen[sp - 1]) {
+                node_seen[sp - 1] = 1;
+                const int n2 = pairwise_left(n);
+                node_o[sp] = o + n2; node_n[sp] = n - n2; node_seen[sp] = 0;                // the right child waits below the left one
+                node_o[sp + 1] = o; node_n[sp + 1] = n2; node_seen[sp + 1] = 0;
+                sp += 2;
+            } else {
+                val_xy[vp - 2] = val_xy[vp - 2] + val_xy[vp - 1];
+                val_xx[vp - 2] = val_xx[vp - 2] + val_xx[vp - 1];
+                --vp;
+                --sp;
+            }
         }
+        sxy += val_xy[0];
+        sxx += val_xx[0];
     }
-    header[0] = val_xy[0];
-    header[1] = val_xx[0];
-    header[2] = val_xy[0] / val_xx[0];                                                  // utils.py:160
+    header[0] = sxy;
+    header[1] = sxx;
+    header[2] = sxy / sxx;                                                              // utils.py:160
 }
 
 // ---- prefix sum of the steps: grid ceil(n / 1024) -----------------------------------------------------------------------------

@@ -614,7 +614,8 @@ int clslam_pcl_resolve(const float* points, const unsigned long long* zbuf, long
  *   ate = sqrt(mean |gt_xyz - pred_xyz|^2) (utils.py:317-328; NaN for n = 0).  rpe_trans / rpe_rot = the means over i < n-1 of
  *   the two errors of inv(inv(gt[i]) @ gt[i+1]) @ (inv(pred[i]) @ pred[i+1]) (utils.py:331-354; NaN for n < 2).
  *   scaling = sum(pred_xyz * gt_xyz) / sum(pred_xyz^2) (utils.py:151-161), always reported (NaN for n = 0); both sums are added
- *   in the order np.sum adds the contiguous (n,3) arrays (numpy's pairwise summation, products rounded on their own), so the
+ *   in the order np.sum adds the contiguous (n,3) arrays (numpy's pairwise summation inside each piece of 8192 elements, the
+ *   pieces one after the other; products rounded on their own), so the
  *   factor is the reference's to the last bit -- calc_error prints all its digits.  With optimize_scale != 0 the
  *   translations of pred are multiplied by it for the SEGMENT errors only; ate and rpe use pred as given (utils.py:374,378).
  *   path_length = dist[n-1].

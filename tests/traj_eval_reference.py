@@ -102,12 +102,57 @@ def segment_frames(dist):
     return first, length, last.astype(np.int64)
 
 
-def decision_margin(dist):
-    """the smallest |dist[i] - (dist[first] + length)| over all rows and frames: how far the segment decisions are from rounding"""
+def decision_margins(dist):
+    """per row, the smallest |dist[i] - (dist[first] + length)| over all frames"""
     first, length, _ = segment_frames(dist)
     limit = dist[first] + length
     j = np.clip(np.searchsorted(dist, limit), 1, len(dist) - 1)
-    return float(np.minimum(np.abs(dist[j] - limit), np.abs(dist[j - 1] - limit)).min())
+    return np.minimum(np.abs(dist[j] - limit), np.abs(dist[j - 1] - limit))
+
+
+def decision_margin(dist):
+    """the smallest |dist[i] - (dist[first] + length)| over all rows and frames: how far the segment decisions are from rounding"""
+    return float(decision_margins(dist).min())
+
+
+def poses_from_xyz(xyz):
+    """(n,3) -> (n,4,4) float64 poses with identity rotations"""
+    xyz = np.asarray(xyz, dtype=np.float64)
+    p = np.broadcast_to(np.eye(4), (len(xyz), 4, 4)).copy()
+    p[:, :3, 3] = xyz
+    return p
+
+
+def lu_inverse(a, tie='first'):
+    """A 4x4 inverse in plain Python floats (binary64, every operation rounded on its own), as csrc/traj_eval.hip documents its
+    own: LU with partial pivoting on [A | I], the pivot of column k being the FIRST row r >= k of the largest |a[r][k]|
+    (tie='last': the last such row -- a deliberately different rule, for the tests that show they can tell the two apart), then
+    back substitution.  -> (inverse as a 4x4 list, [p0, p1, p2, p3] the pivot rows chosen)"""
+    a = [[float(x) for x in row] for row in a]
+    b = [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
+    pivots = []
+    for k in range(4):
+        p, best = k, abs(a[k][k])
+        for r in range(k + 1, 4):
+            v = abs(a[r][k])
+            if v > best or (tie == 'last' and v == best):
+                best, p = v, r
+        pivots.append(p)
+        a[k], a[p] = a[p], a[k]
+        b[k], b[p] = b[p], b[k]
+        for r in range(k + 1, 4):
+            f = a[r][k] / a[k][k]
+            for j in range(k + 1, 4):
+                a[r][j] -= f * a[k][j]
+            for j in range(4):
+                b[r][j] -= f * b[k][j]
+    for k in range(3, -1, -1):
+        for j in range(4):
+            s = b[k][j]
+            for c in range(k + 1, 4):
+                s -= a[k][c] * b[c][j]
+            b[k][j] = s / a[k][k]
+    return b, pivots
 
 
 # ---- one evaluation -----------------------------------------------------------------------------------------------------
@@ -115,6 +160,29 @@ def scale_factor(pred, gt, hp=False):
     dt = HP if hp else np.float64
     X, Y = _as_poses(pred, dt)[:, :3, 3], _as_poses(gt, dt)[:, :3, 3]
     return np.sum(X * Y) / np.sum(X**2)
+
+
+def pairwise_tree_sum(a):
+    """numpy's pairwise summation (pairwise_sum of its add loop) as ONE tree over a 1-D float64 array: more than 128 elements are
+    split at half the length rounded down to a multiple of 8; a leaf of 8..128 runs eight interleaved accumulators, then the
+    remainder one by one; fewer than 8 are added one by one.  np.sum IS this for up to 8192 elements (numpy's buffer size);
+    beyond, numpy sums each 8192-element piece this way and adds the pieces in order -- so for longer arrays this function is
+    NOT np.sum, and the tests use it to show that they can tell the two apart."""
+    n = len(a)
+    if n > 128:
+        h = n // 2
+        h -= h % 8
+        return pairwise_tree_sum(a[:h]) + pairwise_tree_sum(a[h:])
+    m = n - n % 8 if n >= 8 else 0
+    res = np.float64(0.0)
+    if m:
+        r = a[:8].copy()
+        for i in range(8, m, 8):
+            r = r + a[i:i + 8]
+        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+    for x in a[m:]:
+        res = res + x
+    return res
 
 
 def pair_errors(a, b, a_inverted=False, hp=False):
