@@ -176,13 +176,15 @@ _SIGNATURES = {
     'clslam_pcl_splat_scratch': [i32, i32],
     'clslam_pcl_splat': [fptr, fptr, fptr, i32, fptr, fptr, i32, i32, C.c_longlong, C.c_longlong, i32, C.c_double, i32, C.c_void_p],
     'clslam_pcl_resolve': [fptr, fptr, C.c_longlong, fptr, fptr, fptr, i32, i32, i32, C.c_void_p],
+    'clslam_pcl_voxel_sort': [fptr, fptr, fptr, i32, C.c_longlong, C.c_double, i32, C.c_void_p, C.c_void_p],
+    'clslam_pcl_voxel_reduce': [fptr, fptr, fptr, i32, C.c_longlong, C.c_void_p, fptr, fptr, C.c_longlong, C.c_void_p],
     'clslam_pose_pair_error': [fptr, fptr, i32, i32, fptr, C.c_void_p],
     'clslam_traj_metrics_scratch': [i32],
     'clslam_traj_metrics': [fptr, fptr, i32, i32, fptr, fptr, fptr, fptr, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
-ABI_VERSION = 112          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
-_SIZE_FNS = {'clslam_wino_weight_size': [i32, i32]}      # return size_t
+ABI_VERSION = 113          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
+_SIZE_FNS = {'clslam_wino_weight_size': [i32, i32], 'clslam_pcl_voxel_scratch': [C.c_longlong]}      # return size_t
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}
 

@@ -7,6 +7,9 @@ arrays and host tensors are uploaded.  The result comes back as what went in: nu
 array out, which the reference's ``save_point_cloud`` / ``MeshlabInf`` and ``generate_figure`` take unchanged; a tensor in
 gives a tensor on the same device out.  All results are float32.
 
+``voxel_downsample`` reduces a cloud to one mean row per occupied grid cell (a radix sort of the cell keys on the device) and
+``save_point_cloud`` is the reference's (slam/utils.py:61-73) with a trailing ``voxel_size``: the same bytes, written in seconds.
+
 ``DenseMap`` stores every frame's cloud in ITS CAMERA FRAME and poses it when it is read: after a loop-closure ``optimize()``
 the whole map is re-posed from the corrected vertex poses by calling ``world_points`` / ``render`` again -- nothing is cached
 across pose changes.
@@ -127,6 +130,87 @@ def pcl_to_image(pcl, camera_matrix, image_shape):
     return _like(ops.pcl_to_image(points, _camera(camera_matrix, dev), image_shape), pcl)
 
 
+def _voxel_size(fn: str, voxel_size, min_points) -> None:
+    try:
+        ok = float(voxel_size) > 0.0 and np.isfinite(float(voxel_size))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise _lib.ClslamError(f'{fn}: voxel_size must be a finite number above 0, got {voxel_size!r}')
+    if not isinstance(min_points, (int, np.integer)) or isinstance(min_points, bool) or min_points < 1:
+        raise _lib.ClslamError(f'{fn}: min_points must be an integer of at least 1, got {min_points!r}')
+
+
+def voxel_downsample(pcl, voxel_size, min_points: int = 1, return_counts: bool = False):
+    """The voxel-grid filter: one (6,) row per cell of side `voxel_size` that holds at least `min_points` points of the (M,6)
+    cloud -- the float64 mean of its members' coordinates and colours, rounded once to float32 -- in ascending order of
+    (iz, iy, ix), i = floor(c / voxel_size).  Rows with a NaN or an infinity are dropped; a cell index beyond +-2^20 raises.
+    return_counts adds the (V,) int32 number of members of every row."""
+    fn = 'voxel_downsample'
+    _voxel_size(fn, voxel_size, min_points)
+    dev = _device_of(pcl)
+    points = _tensor(pcl, 'pcl', dev)
+    if points.dim() != 2 or points.shape[1] != 6:
+        raise _lib.ClslamError(f'{fn}: a cloud must be (M, 6), got {tuple(points.shape)}')
+    rows, counts = ops.pcl_voxel_downsample(points, voxel_size, min_points=int(min_points))
+    return (_like(rows, pcl), _like(counts, pcl)) if return_counts else _like(rows, pcl)
+
+
+OBJ_CHUNK = 1 << 16         # rows formatted by one % operation
+
+
+def save_point_cloud(filename, pcl, global_pose_list=None, verbose: bool = True, voxel_size: Optional[float] = None) -> None:
+    """slam/utils.py:61-73 with MeshlabInf.add_points / write (slam/meshlab.py:116-139, 159-206; false_color=False, no faces):
+    `pcl` ((M,6) only: the 3- and 4-column clouds add_points paints grey are not taken) -- with `global_pose_list` a list of
+    clouds, accumulated first -- written as "# OBJ file" and one
+    "v x y z r g b" line per point with four decimals; rows with a NaN are dropped, the colours are normalised over the whole
+    cloud (norm_range_01) and shifted so that their maximum is 1.  `voxel_size` thins the cloud with voxel_downsample first.
+    Dropping, thinning and normalising run on the device; the rows cross to the host once, as float64, and are formatted
+    OBJ_CHUNK rows at a time.  The bytes are the reference's for the same float32 cloud.  `verbose` is accepted for the
+    signature's sake: writing a map takes seconds, not the minutes a progress bar is for."""
+    fn = 'save_point_cloud'
+    if voxel_size is not None:
+        _voxel_size(fn, voxel_size, 1)
+    if global_pose_list is not None:
+        cloud = accumulate_pcl(pcl, global_pose_list)
+    else:
+        cloud = pcl
+    dev = _device_of(cloud)
+    points = _tensor(cloud, 'pcl', dev)
+    if points.dim() == 1:
+        points = points.reshape(1, -1)
+    if points.dim() != 2 or points.shape[1] != 6:
+        raise _lib.ClslamError(f'{fn}: a cloud must be (M, 6), got {tuple(points.shape)}')
+    if voxel_size is not None:
+        points, _ = ops.pcl_voxel_downsample(points, voxel_size)
+    _write_obj(filename, points)
+
+
+def _write_obj(filename, points: torch.Tensor) -> None:
+    """(M,6) float32 on any device -> the reference's file"""
+    rows = points[~torch.isnan(points).any(dim=1)].to(torch.float64)
+    if rows.shape[0]:
+        c = rows[:, 3:]
+        lo, hi = c.min(), c.max()
+        span = hi - lo
+        span = torch.where(span < np.finfo(np.float64).eps, torch.ones_like(span), span)
+        c = ((c - lo) / span).clamp(0.0, 1.0)
+        c = c + (1.0 - c.max())
+        # write() passes the coordinates through its identity global_transformation, 1 x + 0 y + 0 z + 0: -0.0 becomes 0.0, an
+        # infinite coordinate stays and turns the row's other two into NaN (0 * inf)
+        inf = torch.isinf(rows[:, :3])
+        others = inf.sum(dim=1, keepdim=True) - inf.to(torch.int64)
+        xyz = torch.where(others > 0, torch.full_like(rows[:, :3], float('nan')), rows[:, :3] + 0.0)
+        rows = torch.cat([xyz, c], dim=1)
+    host = rows.cpu().numpy()
+    line = 'v %.4f %.4f %.4f %.4f %.4f %.4f\n'
+    with open(filename, 'w', encoding='utf-8') as f:
+        f.write('# OBJ file\n')
+        for a in range(0, host.shape[0], OBJ_CHUNK):
+            chunk = host[a:a + OBJ_CHUNK]
+            f.write((line * chunk.shape[0]) % tuple(chunk.ravel().tolist()))
+
+
 class DenseMap:
     """The dense coloured map on the device: one camera-frame cloud per frame in a geometrically grown buffer, host-side
     int64 segment offsets and step ids.
@@ -242,11 +326,21 @@ class DenseMap:
             out[i] = np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m, dtype=np.float64).reshape(4, 4)
         return out
 
-    def world_points(self, poses) -> torch.Tensor:
-        """(M,6) device tensor: every frame's rows posed by ITS pose (world <- camera), in insertion order"""
+    def world_points(self, poses, voxel_size: Optional[float] = None, min_points: int = 1) -> torch.Tensor:
+        """(M,6) device tensor: every frame's rows posed by ITS pose (world <- camera), in insertion order.  With a
+        `voxel_size` the (V,6) voxel_downsample of that cloud instead -- the same bits, but the poses are applied inside the
+        filter and no world copy of the map is made."""
+        if voxel_size is not None:
+            _voxel_size('DenseMap.world_points', voxel_size, min_points)
         frames = list(range(len(self)))
         T = torch.from_numpy(self._frame_poses(poses, frames)).to(self.device)
-        return ops.pcl_transform(self.points, self.offsets, T)
+        if voxel_size is None:
+            return ops.pcl_transform(self.points, self.offsets, T)
+        return ops.pcl_voxel_downsample(self.points, voxel_size, offsets=self.offsets, poses=T, min_points=int(min_points))[0]
+
+    def save(self, filename, poses, voxel_size: Optional[float] = None) -> None:
+        """the posed map as the reference's OBJ point file (save_point_cloud), thinned to `voxel_size` if given"""
+        _write_obj(filename, self.world_points(poses, voxel_size))
 
     def render(self, poses, view_pose, camera_matrix, image_shape, exclude=None, min_z: Optional[float] = None,
                return_dist: bool = False, return_index: bool = False):

@@ -941,6 +941,63 @@ def pcl_to_image(points, K, image_shape, offsets=None, poses=None, min_z=None, r
     return (image, *extra) if extra else image
 
 
+def pcl_voxel_scratch(m: int) -> int:
+    return _query('clslam_pcl_voxel_scratch', m)
+
+
+def pcl_voxel_downsample(points, voxel_size, offsets=None, poses=None, min_points=1, return_info=False):
+    """points (M,6) fp32 [, offsets (F+1) int64 + poses (F,4,4) fp64 applied on the fly, as pcl_transform would] ->
+    (rows (V,6) fp32, counts (V,) int32) on the device: one row per cell of a grid of voxel_size with at least min_points
+    members, in ascending order of key = (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20), i = floor(double(c) / voxel_size);
+    each value is the fp64 mean of the members' fp32 values, rounded once.  Rows with a non-finite value are dropped; a cell
+    index outside [-2^20, 2^20) raises.  The counts of the sort (cells, rows out of range, radix passes run, rows dropped) come
+    back through pinned memory behind an event, 32 bytes; return_info=True appends them as a dict."""
+    fn = 'pcl_voxel_downsample'
+    _cloud('points', fn, points)
+    vs = float(voxel_size)
+    if not (vs > 0.0 and vs != float('inf')):
+        raise _lib.ClslamError(f'{fn}: voxel_size must be finite and above 0, got {voxel_size}')
+    if int(min_points) != min_points or min_points < 1 or min_points >= 1 << 31:
+        raise _lib.ClslamError(f'{fn}: min_points must be an integer of at least 1, got {min_points}')
+    if (offsets is None) != (poses is None):
+        raise _lib.ClslamError(f'{fn}: offsets and poses go together')
+    F = 0
+    if poses is not None:
+        offsets, poses = _segments(fn, points, offsets, poses)
+        F = poses.shape[0]
+    dev, M = points.device, points.shape[0]
+    if M == 0:
+        empty = torch.empty(0, 6, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+        return (*empty, {'cells': 0, 'out_of_range': 0, 'passes': 0, 'dropped': 0}) if return_info else empty
+    words = pcl_voxel_scratch(M)
+    if words <= 0:
+        raise _lib.ClslamError(f'{fn}: one call takes fewer than 2^31 points, got {M}')
+    scratch = torch.empty(words, dtype=torch.int64, device=dev)
+    lib, stream = _lib.get_lib(), _stream(points)
+    lib.call('clslam_pcl_voxel_sort', _p(points), _pl(offsets), _pd(poses), F, M, vs, int(min_points), _pl(scratch), stream)
+    if scratch.is_cuda:
+        host = torch.empty(4, dtype=torch.int64, pin_memory=True)
+        if _FORCED_STREAM is None:
+            host.copy_(scratch[2:6], non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(dev))
+            event.synchronize()
+        else:                                   # a launch_on() stream torch does not know: wait for it as a whole
+            torch.cuda.synchronize(dev)
+            host.copy_(scratch[2:6])
+    else:
+        host = scratch[2:6]
+    cells, out_of_range, passes, dropped = (int(v) for v in host)
+    if out_of_range:
+        raise _lib.ClslamError(f'{fn}: {out_of_range} of {M} points fall into cells beyond index -2^20 .. 2^20 - 1 at voxel_size {vs}')
+    rows = torch.empty(cells, 6, device=dev)
+    counts = torch.empty(cells, dtype=torch.int32, device=dev)
+    lib.call('clslam_pcl_voxel_reduce', _p(points), _pl(offsets), _pd(poses), F, M, _pl(scratch), _p(rows) if cells else None,
+             _pi(counts) if cells else None, cells, stream)
+    info = {'cells': cells, 'out_of_range': out_of_range, 'passes': passes, 'dropped': dropped}
+    return (rows, counts, info) if return_info else (rows, counts)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # Frame store of the replay ingest (clslam_store_*, include/clslam_hip.h)
 def store_pack(planes, offsets, slot: torch.Tensor, inexact: torch.Tensor) -> None:

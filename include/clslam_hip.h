@@ -44,8 +44,9 @@ extern "C" {
  * 107 = the range forms of 104 and the unfused pyramid backward removed; 108 = clslam_store_* added (frame store);
  * 109 = the batched-copy and the fused reduction + Adam entry points removed (DESIGN.md "Retired step paths");
  * 110 = clslam_pose_pair_error, clslam_traj_metrics* added; 111 = clslam_resize_level_u8, clslam_ring_gather added (online ingest).
+ * 112 = clslam_pair_loss added (predict_from_images); 113 = clslam_pcl_voxel_* added (voxel-grid downsampling of a cloud).
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 112
+#define CLSLAM_ABI_VERSION 113
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -580,7 +581,23 @@ int clslam_depth_metrics(const float* pred, const float* gt, float* out, void* s
  * clslam_pcl_resolve: image (rows,cols,3) = the winner's colour, 0 where empty (:48); optional dist (rows,cols) = its distance,
  * +inf where empty; optional index (rows,cols) int64 = its row in `points`, -1 where empty.  merge != 0 (needs dist): the planes
  * hold the result of earlier launches over lower indices and change only where this launch's winner is strictly closer -- how a
- * cloud of more than 2^32 points is rendered in several launches.                                                              */
+ * cloud of more than 2^32 points is rendered in several launches.
+ *
+ * clslam_pcl_voxel_sort + clslam_pcl_voxel_reduce: the voxel-grid filter, one row per occupied cell.  points (m,6), 1 <= m < 2^31;
+ * with poses != NULL each point is first posed as by clslam_pcl_transform (including the rounding to fp32), so the result equals
+ * that of the filter on the transformed cloud bitwise.  voxel_size: finite, > 0.  Per axis the cell index is
+ * floor((double)c / voxel_size): one IEEE fp64 division and one floor.  A row with a non-finite value among its six (a NaN pose
+ * makes its whole segment such) is dropped.  A row with an index outside [-2^20, 2^20 - 1] is dropped and counted: an error for
+ * the caller to raise.  key = (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20); the cells come out in ascending key order, those
+ * with at least min_points (>= 1) members only.  clslam_pcl_voxel_sort forms the keys, sorts (key, point index) by a stable LSD
+ * radix sort of 4-bit digits that skips the digits in which all keys agree, and lists the first position of every kept cell.  It
+ * leaves four 64-bit words at scratch + 16 bytes: the number of kept cells, the rows with an index out of range, the radix passes
+ * run, the rows dropped (the out-of-range ones included).  The caller reads them back, allocates, and calls
+ * clslam_pcl_voxel_reduce with n_cells = the first word and the SAME points, offsets, poses and scratch: rows (n_cells,6) fp32 =
+ * per value the fp64 sum of the members' fp32 values divided by their number in fp64, rounded once to fp32; counts (n_cells)
+ * int32.  The members are added in an order that depends on their number and their point indices alone (no floating-point
+ * atomics): two calls agree bitwise.  scratch: clslam_pcl_voxel_scratch(m) 8-byte words (0 = m out of range), 16-byte aligned:
+ * 24 bytes per point (two key and two index buffers) + 1/16 byte per point of histograms + 192 bytes.                          */
 int clslam_pcl_backproject_scratch(int n_images, int h, int w);
 int clslam_pcl_backproject(const float* depth, const float* inv_k, const float* image, float* points, long long* offsets,
                            void* scratch, int n_images, int h, int w, float dist_threshold, void* stream);
@@ -592,6 +609,11 @@ int clslam_pcl_splat(const float* points, const long long* offsets, const double
                      double min_z, int clear, void* stream);
 int clslam_pcl_resolve(const float* points, const unsigned long long* zbuf, long long point_base, float* image, float* dist,
                        long long* index, int rows, int cols, int merge, void* stream);
+size_t clslam_pcl_voxel_scratch(long long m);
+int clslam_pcl_voxel_sort(const float* points, const long long* offsets, const double* poses, int n_segments, long long m,
+                          double voxel_size, int min_points, void* scratch, void* stream);
+int clslam_pcl_voxel_reduce(const float* points, const long long* offsets, const double* poses, int n_segments, long long m,
+                            const void* scratch, float* rows, int* counts, long long n_cells, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Trajectory and pose-error metrics (csrc/traj_eval.hip).  Poses are (n,4,4) row-major fp64 on the device, all arithmetic is
