@@ -18,6 +18,7 @@ ACT_NONE, ACT_RELU, ACT_ELU, ACT_HSWISH, ACT_HSIGMOID = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
 DEPTH_EVAL_MEDIAN_SCALING, DEPTH_EVAL_FROM_DISP, DEPTH_EVAL_NO_MAX = 1, 2, 4
 TRAJ_MAX_POSES = 1 << 20             # include/clslam_hip.h CLSLAM_TRAJ_MAX_POSES
+BAYER_PATTERNS = {'rggb': 0, 'bggr': 1, 'grbg': 2, 'gbrg': 3}      # CLSLAM_BAYER_*
 
 fptr = C.c_void_p
 i32 = C.c_int32
@@ -181,9 +182,12 @@ _SIGNATURES = {
     'clslam_pose_pair_error': [fptr, fptr, i32, i32, fptr, C.c_void_p],
     'clslam_traj_metrics_scratch': [i32],
     'clslam_traj_metrics': [fptr, fptr, i32, i32, fptr, fptr, fptr, fptr, C.c_void_p],
+    'clslam_demosaic_bilinear': [C.c_void_p, fptr, i32, i32, i32, i32, C.c_void_p],
+    'clslam_undistort_lut': [C.c_void_p, fptr, C.c_void_p, i32, i32, i32, i32, i32, C.c_void_p],
+    'clslam_robotcar_rectify': [C.c_void_p, fptr, C.c_void_p, i32, i32, i32, i32, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
-ABI_VERSION = 113          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
+ABI_VERSION = 114          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32], 'clslam_pcl_voxel_scratch': [C.c_longlong]}      # return size_t
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}

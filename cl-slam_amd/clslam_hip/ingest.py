@@ -707,11 +707,17 @@ class OnlineSampleBuilder:
 
     Covers the driver's configuration (slam/slam.py:44-72): no augmentation, one view, neither masks nor ground-truth depth;
     anything else raises ValueError here, not at the first frame.  Kitti and Robotcar expose the same attributes
-    (datasets/robotcar.py:220-270 is kitti.py:231-317 without the depth branch) and go through the same code."""
+    (datasets/robotcar.py:220-270 is kitti.py:231-317 without the depth branch) and go through the same code.
+
+    ``camera_model`` (a clslam_hip.robotcar.CameraModel): the dataset's PNGs are RobotCar's RAW frames, as downloaded.  Each is
+    read as one channel, uploaded, and demosaiced and undistorted by one fused launch in front of ``FrameRing.put``, so the
+    reference's offline pass (datasets/robotcar.py:493-548) is not needed.  The frame keeps its size; the dataset's camera matrix
+    (normalised by that size, robotcar.py _load_camera_calibration) is used as it is."""
 
     _NEEDS = ('frame_ids', 'scales', 'height', 'width', 'camera_matrix', 'relative_distances', '_pre_getitem', '_scale_camera_matrix')
 
-    def __init__(self, dataset, device='cuda', ring_frames: int = 8, prefetch: int = 2, decode_threads: int = 2) -> None:
+    def __init__(self, dataset, device='cuda', ring_frames: int = 8, prefetch: int = 2, decode_threads: int = 2,
+                 camera_model=None) -> None:
         for name in self._NEEDS:
             if not hasattr(dataset, name):
                 raise ValueError(f'OnlineSampleBuilder: the dataset has no `{name}` (a datasets.Kitti / Robotcar object is expected)')
@@ -742,12 +748,20 @@ class OnlineSampleBuilder:
         self._decoded: Dict = {}                        # path -> Future of the decoded (page-locked) frame, oldest first
         self._matrices = None
         self._per_sample = sum(3 * h * w for h, w in self.ring.sizes) * len(self.frame_ids)
+        # a robotcar.CameraModel: the dataset's files are RAW frames (one-channel Bayer mosaics, distorted), rectified on the device
+        self.camera_model = camera_model
 
     # ------------------------------------------------------------------------------------------------------------------
     def _decode_file(self, path) -> torch.Tensor:
         import numpy as np
         from PIL import Image
-        img = torch.from_numpy(np.asarray(Image.open(path).convert('RGB')).copy())            # datasets/kitti.py:249
+        if self.camera_model is None:
+            img = torch.from_numpy(np.asarray(Image.open(path).convert('RGB')).copy())        # datasets/kitti.py:249
+        else:
+            img = torch.from_numpy(np.array(Image.open(path)))                                # the mosaic: a third of the bytes
+            if img.dim() != 2 or img.dtype is not torch.uint8:
+                raise ValueError(f'OnlineSampleBuilder: camera_model is set, but {path} is no one-channel 8-bit raw frame '
+                                 f'({tuple(img.shape)} {img.dtype})')
         return img.pin_memory() if self.device.type == 'cuda' else img
 
     def _submit(self, path) -> None:
@@ -773,7 +787,10 @@ class OnlineSampleBuilder:
         for p in misses:
             fut = self._decoded.pop(p, None)
             raw = self._decode_file(p) if fut is None or fut.cancelled() else fut.result()
-            self.ring.put(p, raw.to(self.device, non_blocking=True), keep=paths)
+            raw = raw.to(self.device, non_blocking=True)
+            if self.camera_model is not None:                             # datasets/robotcar.py:522-548 in one launch
+                raw = self.camera_model.rectify(raw)
+            self.ring.put(p, raw, keep=paths)
 
     def _host_item(self, shifted: int) -> Dict:
         """the non-image entries of dataset[index], un-collated, in the dataset's key order"""

@@ -1088,3 +1088,78 @@ def ring_gather(ring: torch.Tensor, slot_bytes: int, offsets, sizes, slots, rgb,
                 raise _lib.ClslamError(f'ring_gather: entry {t} needs 3 x {h} x {w} values, got {tuple(out.shape)}')
         desc.rgb[t], desc.aug[t] = _p(rgb[t]), _p(aug[t])
     _lib.get_lib().call('clslam_ring_gather', C.byref(desc), _pa(ring, torch.uint8), _stream(ring))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# RobotCar raw frames (csrc/robotcar.hip; the reference's names are in clslam_hip/robotcar.py)
+def _bayer(fn: str, pattern) -> int:
+    code = _lib.BAYER_PATTERNS.get(pattern.lower() if isinstance(pattern, str) else pattern)
+    if code is None:
+        raise ValueError(f'{fn}: pattern must be one of {sorted(_lib.BAYER_PATTERNS)}, got {pattern!r}')
+    return code
+
+
+def _frames(fn: str, name: str, t, rank: int, dtypes) -> None:
+    if not isinstance(t, torch.Tensor) or t.dim() != rank or t.dtype not in dtypes:
+        raise _lib.ClslamError(f'{fn}: {name} must be a tensor of rank {rank} and dtype {" or ".join(str(d) for d in dtypes)}, got '
+                               f'{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}')
+    if t.numel() and min(t.shape[1:]) == 0:
+        raise _lib.ClslamError(f'{fn}: {name} has an empty plane, {tuple(t.shape)}')
+
+
+def _lut(fn: str, lut, like: torch.Tensor) -> None:
+    """the (2,H,W) float64 table of (row, col) source coordinates for frames shaped like `like` (N,H,W,...), on their device"""
+    H, W = like.shape[1], like.shape[2]
+    if not isinstance(lut, torch.Tensor) or lut.dtype is not torch.float64 or tuple(lut.shape) != (2, H, W):
+        raise _lib.ClslamError(f'{fn}: lut must be a {(2, H, W)} float64 tensor for frames of {H}x{W}, got '
+                               f'{(tuple(lut.shape), lut.dtype) if isinstance(lut, torch.Tensor) else type(lut).__name__}')
+    if lut.device != like.device:
+        raise _lib.ClslamError(f'{fn}: lut on {lut.device}, the frames on {like.device}')
+
+
+def _out_like(fn: str, out, shape, dtype, like: torch.Tensor) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype is not dtype or out.device != like.device:
+        raise _lib.ClslamError(f'{fn}: out must be {tuple(shape)} {dtype} on {like.device}, got {tuple(out.shape)} {out.dtype} on {out.device}')
+    return out
+
+
+def demosaic_bilinear(cfa, pattern, out=None):
+    """cfa (N,H,W) uint8 Bayer mosaic -> (N,H,W,3) float64: colour_demosaicing.demosaicing_CFA_Bayer_bilinear (datasets/robotcar.py:544),
+    borders by scipy.ndimage's 'reflect'"""
+    fn = 'demosaic_bilinear'
+    code = _bayer(fn, pattern)
+    _frames(fn, 'cfa', cfa, 3, (torch.uint8,))
+    N, H, W = cfa.shape
+    out = _out_like(fn, out, (N, H, W, 3), torch.float64, cfa)
+    for n0 in range(0, N, 65535):
+        n = min(65535, N - n0)
+        _lib.get_lib().call('clslam_demosaic_bilinear', _pa(cfa[n0:n0 + n], torch.uint8), _pd(out[n0:n0 + n]), n, H, W, code, _stream(cfa))
+    return out
+
+
+def undistort_lut(image, lut, out=None):
+    """image (N,H,W,C) uint8 or float64, lut (2,H,W) float64 (row, col) -> the same shape and dtype: per channel
+    scipy.ndimage.map_coordinates(order=1, mode='constant', cval=0) (datasets/robotcar.py:631-642); uint8 = trunc(t) & 255"""
+    fn = 'undistort_lut'
+    _frames(fn, 'image', image, 4, (torch.uint8, torch.float64))
+    _lut(fn, lut, image)
+    N, H, W, Cn = image.shape
+    out = _out_like(fn, out, image.shape, image.dtype, image)
+    _lib.get_lib().call('clslam_undistort_lut', _pa(image, image.dtype), _pd(lut), _pa(out, image.dtype), N, H, W, Cn,
+                        int(image.dtype is torch.float64), _stream(image))
+    return out
+
+
+def robotcar_rectify(cfa, lut, pattern, out=None):
+    """cfa (N,H,W) uint8 raw frames, lut (2,H,W) float64 -> (N,H,W,3) uint8 = undistort_lut(demosaic_bilinear(cfa)) as uint8, one
+    launch, no float64 image in memory (datasets/robotcar.py:522-548 _load_image with a model)"""
+    fn = 'robotcar_rectify'
+    code = _bayer(fn, pattern)
+    _frames(fn, 'cfa', cfa, 3, (torch.uint8,))
+    _lut(fn, lut, cfa)
+    N, H, W = cfa.shape
+    out = _out_like(fn, out, (N, H, W, 3), torch.uint8, cfa)
+    _lib.get_lib().call('clslam_robotcar_rectify', _pa(cfa, torch.uint8), _pd(lut), _pa(out, torch.uint8), N, H, W, code, _stream(cfa))
+    return out

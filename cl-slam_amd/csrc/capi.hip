@@ -153,7 +153,7 @@ extern "C" int clslam_handoff_wait(void* event, void* producer_stream, void* con
 // 109: the batched-copy and the fused reduction + Adam entry points removed (the captured training step went with them)
 // 110: clslam_pose_pair_error, clslam_traj_metrics* (additive)
 // 112: clslam_pair_loss* (additive)
-extern "C" int clslam_version(void) { return 113; }
+extern "C" int clslam_version(void) { return 114; }
 // identity of the kernel sources this library was LINKED from (csrc/build.py passes it when it compiles this file, which it
 // does whenever any object is rebuilt): read from the loaded library, not from a file beside it
 #ifndef CLSLAM_BUILD_ID

@@ -45,8 +45,9 @@ extern "C" {
  * 109 = the batched-copy and the fused reduction + Adam entry points removed (DESIGN.md "Retired step paths");
  * 110 = clslam_pose_pair_error, clslam_traj_metrics* added; 111 = clslam_resize_level_u8, clslam_ring_gather added (online ingest).
  * 112 = clslam_pair_loss added (predict_from_images); 113 = clslam_pcl_voxel_* added (voxel-grid downsampling of a cloud).
+ * 114 = clslam_demosaic_bilinear, clslam_undistort_lut, clslam_robotcar_rectify added (RobotCar raw frames).
  * Bindings check it before the first call.                                                                                    */
-#define CLSLAM_ABI_VERSION 113
+#define CLSLAM_ABI_VERSION 114
 int clslam_version(void);
 const char* clslam_last_error(void);
 const char* clslam_last_error_string(void); /* = clslam_last_error (the name SURVEY.md 8b lists) */
@@ -684,6 +685,42 @@ int clslam_resize_level_u8(const unsigned char* src, unsigned char* dst, long lo
                            const int* coeffs_h, int ksize_h, const int* bounds_v, const int* coeffs_v, int ksize_v, int batch,
                            int in_h, int in_w, int ch, int out_h, int out_w, void* stream);
 int clslam_ring_gather(const clslam_ring_gather_desc* desc, const unsigned char* ring, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * RobotCar raw frames (csrc/robotcar.hip): stereo/centre/<timestamp>.png is a one-channel Bayer mosaic seen through a distorting lens,
+ * and the reference reads it only after its offline pass (datasets/robotcar.py:493-548, undistort_images / _load_image) has
+ * rewritten the sequence.  Images are contiguous, channels LAST; a launch takes n frames of one size.
+ *
+ * clslam_demosaic_bilinear replaces colour_demosaicing.demosaicing_CFA_Bayer_bilinear (robotcar.py:544): cfa (n,h,w) uint8 ->
+ * out (n,h,w,3) float64, R = conv(CFA * R_m, H_RB), G = conv(CFA * G_m, H_G), B = conv(CFA * B_m, H_RB), H_G = [[0,1,0],[1,4,1],
+ * [0,1,0]] / 4, H_RB = [[1,2,1],[2,4,2],[1,2,1]] / 4, with mask[c][y::2, x::2] = 1 for (c, (y, x)) in zip(pattern, [(0,0), (0,1),
+ * (1,0), (1,1)]).  Every value is a multiple of 1/4: the result does not depend on the order of the sum.  BORDER: scipy.ndimage.
+ * convolve's default 'reflect' (d c b a | a b c d) on the masked planes.  This rule is RESTATED from the libraries' documentation
+ * and was NOT COMPARED against colour_demosaicing (not installed where this was written; so was cv2.resize for the depth
+ * metrics); only the outermost pixel ring depends on it, and there the result can exceed 255.  n <= 65535.
+ *
+ * clslam_undistort_lut replaces CameraModel.undistort (robotcar.py:617-642; one scipy.ndimage.map_coordinates(order=1,
+ * mode='constant', cval=0) per channel): image, out (n,h,w,c) uint8 (is_f64 = 0) or float64 (is_f64 = 1), distinct; lut (2,h,w)
+ * float64 = (row, col) of the source sample of every output pixel, shared by the n frames and read once per element, not once
+ * per frame.  Inside iff 0 <= row <= h-1 and 0 <= col <= w-1, else 0.  r0 = floor(row), sy = 1 - (row - r0), ty = 1 - sy (the
+ * library's last weight is one minus the others, not row - r0 again), second tap clamped to h-1 (weight 0 there), the same for
+ * col;  t = 0; t += (v00*sy)*sx; t += (v01*sy)*tx; t += (v10*ty)*sx; t += (v11*ty)*tx, every operation rounded on its own: scipy's
+ * float64 to the last bit.  uint8 output = (int64)t & 255 (truncation
+ * toward zero, then the low byte; the reference's astype(np.uint8) of a value above 255 is platform-defined).
+ *
+ * clslam_robotcar_rectify replaces _load_image(path, model) (robotcar.py:522-548) for n raw frames in ONE launch: cfa (n,h,w) uint8
+ * -> out (n,h,w,3) uint8 = clslam_undistort_lut(clslam_demosaic_bilinear(cfa)) converted as above, byte for byte, with the four
+ * demosaiced taps of a pixel formed in registers: no float64 image is written.  The table is read once per pixel.
+ *
+ * h * w * channels <= 2^30.  n = 0 is a no-op.                                                                                  */
+#define CLSLAM_BAYER_RGGB 0
+#define CLSLAM_BAYER_BGGR 1
+#define CLSLAM_BAYER_GRBG 2
+#define CLSLAM_BAYER_GBRG 3
+int clslam_demosaic_bilinear(const unsigned char* cfa, double* out, int n, int h, int w, int pattern, void* stream);
+int clslam_undistort_lut(const void* image, const double* lut, void* out, int n, int h, int w, int c, int is_f64, void* stream);
+int clslam_robotcar_rectify(const unsigned char* cfa, const double* lut, unsigned char* out, int n, int h, int w, int pattern,
+                            void* stream);
 
 #ifdef __cplusplus
 }
