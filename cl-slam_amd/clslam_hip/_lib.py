@@ -16,6 +16,8 @@ LIB_PATH = Path(__file__).resolve().parents[1] / 'lib' / 'libclslam_hip.so'
 OK = 0
 ACT_NONE, ACT_RELU, ACT_ELU, ACT_HSWISH, ACT_HSIGMOID = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
+PNG_BLOCK, PNG_FILTER_ADAPTIVE = 16384, -1                           # CLSLAM_PNG_BLOCK, CLSLAM_PNG_FILTER_ADAPTIVE
+PNG_FILTERS = {'adaptive': PNG_FILTER_ADAPTIVE, 'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4}
 DEPTH_EVAL_MEDIAN_SCALING, DEPTH_EVAL_FROM_DISP, DEPTH_EVAL_NO_MAX = 1, 2, 4
 TRAJ_MAX_POSES = 1 << 20             # include/clslam_hip.h CLSLAM_TRAJ_MAX_POSES
 BAYER_PATTERNS = {'rggb': 0, 'bggr': 1, 'grbg': 2, 'gbrg': 3}      # CLSLAM_BAYER_*
@@ -185,16 +187,41 @@ _SIGNATURES = {
     'clslam_demosaic_bilinear': [C.c_void_p, fptr, i32, i32, i32, i32, C.c_void_p],
     'clslam_undistort_lut': [C.c_void_p, fptr, C.c_void_p, i32, i32, i32, i32, i32, C.c_void_p],
     'clslam_robotcar_rectify': [C.c_void_p, fptr, C.c_void_p, i32, i32, i32, i32, C.c_void_p],
+    'clslam_png_filter': [C.c_void_p, C.c_void_p, C.c_longlong, i32, i32, i32, i32, i32, C.c_void_p],
+    'clslam_png_deflate': [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, i32, i32, i32, i32,
+                           C.c_void_p],
+    'clslam_png_encode': [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, i32, i32, i32, i32, i32,
+                          C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
 ABI_VERSION = 114          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32], 'clslam_pcl_voxel_scratch': [C.c_longlong]}      # return size_t
+_I64_FNS = {'clslam_png_bound': [i32, i32, i32], 'clslam_png_scratch': [i32, i32, i32, i32]}       # return long long
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}
 
 
 class ClslamError(RuntimeError):
     pass
+
+
+def bind_entry_points(cdll, path='the library') -> None:
+    """Set restype / argtypes of every entry point of include/clslam_hip.h on `cdll`.  The ABI number says the descriptors' layout;
+    entry points added without changing it (clslam_png_*, ABI 114) are missing from a library built before them: that is a
+    ClslamError naming the entry point and the remedy, not an AttributeError."""
+    tables = [(_RESTYPES, None), (_SIZE_FNS, C.c_size_t), (_I64_FNS, C.c_longlong), (_PTR_FNS, C.c_void_p), (_VOID_FNS, None),
+              (_SIGNATURES, C.c_int)]
+    for table, restype in tables:
+        for name, spec in table.items():
+            try:
+                fn = getattr(cdll, name)
+            except AttributeError:
+                raise ClslamError(f'{path} does not export {name}: it was built before this entry point was added, rebuild it '
+                                  'with `python cl-slam_amd/csrc/build.py`') from None
+            if table is _RESTYPES:
+                fn.restype, fn.argtypes = spec, []
+            else:
+                fn.restype, fn.argtypes = restype, spec
 
 
 class Library:
@@ -214,22 +241,7 @@ class Library:
         if got != ABI_VERSION:      # a stale library would read the descriptors with another layout: refuse instead of corrupting memory
             raise ClslamError(f'{path} implements ABI version {got}, this binding needs {ABI_VERSION}: rebuild it with '
                               '`python cl-slam_amd/csrc/build.py`')
-        for name, rt in _RESTYPES.items():
-            fn = getattr(self.cdll, name)
-            fn.restype, fn.argtypes = rt, []
-        for name, argtypes in _SIZE_FNS.items():
-            fn = getattr(self.cdll, name)
-            fn.restype, fn.argtypes = C.c_size_t, argtypes
-        for name, argtypes in _PTR_FNS.items():
-            fn = getattr(self.cdll, name)
-            fn.restype, fn.argtypes = C.c_void_p, argtypes
-        for name, argtypes in _VOID_FNS.items():
-            fn = getattr(self.cdll, name)
-            fn.restype, fn.argtypes = None, argtypes
-        for name, argtypes in _SIGNATURES.items():
-            fn = getattr(self.cdll, name)  # AttributeError if the symbol is not exported
-            fn.argtypes = argtypes
-            fn.restype = C.c_int
+        bind_entry_points(self.cdll, path)
         self.is_device = bool(self.cdll.clslam_is_device_build())
         if require_device and not self.is_device:
             raise ClslamError(f'{path} is not a gfx950 device build')
@@ -262,7 +274,7 @@ def install_library_for_tests(path) -> Library:
 
 
 def exported_symbols():
-    return list(_RESTYPES) + list(_SIZE_FNS) + list(_PTR_FNS) + list(_VOID_FNS) + list(_SIGNATURES)
+    return list(_RESTYPES) + list(_SIZE_FNS) + list(_I64_FNS) + list(_PTR_FNS) + list(_VOID_FNS) + list(_SIGNATURES)
 
 
 def build_id() -> str:

@@ -1163,3 +1163,86 @@ def robotcar_rectify(cfa, lut, pattern, out=None):
     out = _out_like(fn, out, (N, H, W, 3), torch.uint8, cfa)
     _lib.get_lib().call('clslam_robotcar_rectify', _pa(cfa, torch.uint8), _pd(lut), _pa(out, torch.uint8), N, H, W, code, _stream(cfa))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# PNG encoding (csrc/png_encode.hip; the user-facing names are in clslam_hip/png.py)
+def _png_filter_code(fn: str, filter) -> int:
+    code = _lib.PNG_FILTERS.get(filter.lower()) if isinstance(filter, str) else filter
+    if isinstance(code, bool) or not isinstance(code, int) or not (_lib.PNG_FILTER_ADAPTIVE <= code <= 4):
+        raise _lib.ClslamError(f'{fn}: filter must be one of {sorted(_lib.PNG_FILTERS)} or a type 0..4, got {filter!r}')
+    return code
+
+
+def _png_images(fn: str, images):
+    """(N,H,W) or (N,H,W,3) contiguous uint8 on the kernels' device -> (N, H, W, channels, filtered bytes per image)"""
+    if not isinstance(images, torch.Tensor) or images.dtype is not torch.uint8 or images.dim() not in (3, 4) \
+            or (images.dim() == 4 and images.shape[3] != 3):
+        raise _lib.ClslamError(f'{fn}: images must be an (N,H,W) or (N,H,W,3) uint8 tensor, got '
+                               f'{(tuple(images.shape), images.dtype) if isinstance(images, torch.Tensor) else type(images).__name__}')
+    if not images.is_contiguous():
+        raise _lib.ClslamError(f'{fn}: images must be contiguous')
+    N, H, W = images.shape[:3]
+    Cn = 3 if images.dim() == 4 else 1
+    if png_bound(H, W, Cn) == 0:
+        raise _lib.ClslamError(f'{fn}: images of {H}x{W}x{Cn} are not taken (H, W >= 1, at most 2^27 filtered bytes each)')
+    return N, H, W, Cn, H * (1 + W * Cn)
+
+
+def png_bound(h: int, w: int, channels: int) -> int:
+    """worst-case size of the PNG file of an (h, w[, 3]) uint8 image (clslam_png_bound; 0: a geometry the library does not take)"""
+    return int(_query('clslam_png_bound', int(h), int(w), int(channels)))
+
+
+def png_filter(images, filter=_lib.PNG_FILTER_ADAPTIVE, out=None):
+    """images (N,H,W) or (N,H,W,3) uint8 -> (N, H * (1 + W * channels)) uint8: every scanline behind its filter type byte
+    (RFC 2083 section 6).  filter 'adaptive' (per row the smallest sum of min(b, 256 - b), ties to the lowest type) or a type 0..4."""
+    fn = 'png_filter'
+    code = _png_filter_code(fn, filter)
+    N, H, W, Cn, F = _png_images(fn, images)
+    out = _out_like(fn, out, (N, F), torch.uint8, images)
+    _lib.get_lib().call('clslam_png_filter', _pa(images, torch.uint8), _pa(out, torch.uint8), F, N, H, W, Cn, code, _stream(images))
+    return out
+
+
+def _png_files(fn: str, out, N: int, H: int, W: int, Cn: int, like: torch.Tensor):
+    """-> (files (N, stride) uint8, lengths (N,) int32): stride >= clslam_png_bound, a multiple of 4"""
+    bound = png_bound(H, W, Cn)
+    if out is None:
+        out = torch.empty((N, (bound + 3) & ~3), dtype=torch.uint8, device=like.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype is not torch.uint8 or out.dim() != 2 or out.shape[0] != N \
+            or out.device != like.device or not out.is_contiguous():
+        raise _lib.ClslamError(f'{fn}: out must be a contiguous ({N}, >= {bound}) uint8 tensor on {like.device}')
+    return out, torch.empty((N,), dtype=torch.int32, device=like.device)
+
+
+def png_deflate(filtered, h: int, w: int, channels: int, out=None):
+    """filtered (N, F >= h * (1 + w * channels)) uint8, rows 16-byte aligned -> (files (N, stride) uint8, lengths (N,) int32): the
+    complete PNG file of every filtered stream, literal-only dynamic / stored deflate blocks of 16 KiB (include/clslam_hip.h)"""
+    fn = 'png_deflate'
+    if not isinstance(filtered, torch.Tensor) or filtered.dtype is not torch.uint8 or filtered.dim() != 2:
+        raise _lib.ClslamError(f'{fn}: filtered must be an (N, F) uint8 tensor')
+    N = filtered.shape[0]
+    if png_bound(h, w, channels) == 0:
+        raise _lib.ClslamError(f'{fn}: images of {h}x{w}x{channels} are not taken')
+    out, lengths = _png_files(fn, out, N, h, w, channels, filtered)
+    nbytes = int(_query('clslam_png_scratch', N, int(h), int(w), int(channels)))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=filtered.device)
+    _lib.get_lib().call('clslam_png_deflate', _pa(filtered, torch.uint8), filtered.shape[1], _pa(out, torch.uint8), out.shape[1],
+                        _pa(lengths, torch.int32), _pa(scratch, torch.uint8), nbytes, N, int(h), int(w), int(channels),
+                        _stream(filtered))
+    return out, lengths
+
+
+def png_encode(images, filter=_lib.PNG_FILTER_ADAPTIVE, out=None):
+    """images (N,H,W) or (N,H,W,3) uint8 -> (files (N, stride) uint8, lengths (N,) int32): file i is files[i, :lengths[i]].  One set
+    of launches for the batch, nothing synchronises; `out` (N, >= png_bound(H, W, channels), a multiple of 4) is overwritten."""
+    fn = 'png_encode'
+    code = _png_filter_code(fn, filter)
+    N, H, W, Cn, _ = _png_images(fn, images)
+    out, lengths = _png_files(fn, out, N, H, W, Cn, images)
+    nbytes = int(_query('clslam_png_scratch', N, H, W, Cn))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=images.device)
+    _lib.get_lib().call('clslam_png_encode', _pa(images, torch.uint8), _pa(out, torch.uint8), out.shape[1], _pa(lengths, torch.int32),
+                        _pa(scratch, torch.uint8), nbytes, N, H, W, Cn, code, _stream(images))
+    return out, lengths

@@ -9,7 +9,8 @@ core) has rewritten it.  Here:
 ``demosaic(cfa, pattern)``                  float64 RGB of a mosaic (csrc/robotcar.hip, clslam_demosaic_bilinear)
 ``CameraModel.undistort(image)``            the table look-up of an (H,W,C) image (clslam_undistort_lut)
 ``load_image(path_or_u8, model, debayer)``  the reference's ``_load_image``; with a model, ONE fused launch
-``undistort_images(...)``                   the offline pass, GPU work in batches, PNG decode / encode on a small thread pool
+``undistort_images(...)``                   the offline pass, GPU work in batches, PNG decode / encode on a small thread pool;
+                                            ``encoder='device'`` encodes on the GPU as well (clslam_hip.png)
 ``OnlineSampleBuilder(dataset, camera_model=model)`` (ingest.py) rectifies raw frames on their way into the ring: no offline pass.
 
 numpy in gives numpy out, a tensor in gives a tensor (on the kernels' device) out.
@@ -27,7 +28,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, png
 
 BAYER_STEREO, BAYER_MONO = 'gbrg', 'rggb'                                  # robotcar.py:530-531
 # robotcar.py:503: "the other photos are overexposed or taken when the car was not (yet) on the road"
@@ -142,8 +143,9 @@ class CameraModel:
         out = ops.undistort_lut(work[None], self.lut(shape[0], shape[1], t.device))[0]
         return _back(out.to(t.dtype), as_numpy)
 
-    def rectify(self, cfa):
-        """(H,W) or (N,H,W) uint8 raw mosaic -> (H,W,3) or (N,H,W,3) uint8 rectified RGB, one fused launch (_load_image, :522-548)"""
+    def rectify(self, cfa, on_device: bool = False):
+        """(H,W) or (N,H,W) uint8 raw mosaic -> (H,W,3) or (N,H,W,3) uint8 rectified RGB, one fused launch (_load_image, :522-548).
+        on_device=True hands back the device tensor whatever came in (undistort_images' device encoder reads it there)."""
         shape = tuple(cfa.shape)
         if len(shape) not in (2, 3):
             raise ValueError(f'CameraModel.rectify: an (H,W) or (N,H,W) raw mosaic is expected, got {shape}')
@@ -151,7 +153,7 @@ class CameraModel:
             raise ValueError('Incorrect image size for camera model')
         t, as_numpy = _to_device(cfa)
         out = ops.robotcar_rectify(t if t.dim() == 3 else t[None], self.lut(shape[-2], shape[-1], t.device), self.pattern)
-        return _back(out if t.dim() == 3 else out[0], as_numpy)
+        return _back(out if t.dim() == 3 else out[0], as_numpy and not on_device)
 
 
 def demosaic(cfa, pattern):
@@ -209,13 +211,18 @@ def _default_workers() -> int:
         return 4
 
 
-def undistort_images(data_path_in, models_path, data_path_out=None, batch: int = 8, workers=None) -> None:
+def undistort_images(data_path_in, models_path, data_path_out=None, batch: int = 8, workers=None, encoder: str = 'pillow') -> None:
     """The reference's offline pass (robotcar.py:493-517).  data_path_out=None is the reference: data_path_in is renamed to
     ``<data_path_in>_distorted`` and the rectified frames FRAME_SLICE of it are written under the old name; with data_path_out
     nothing is renamed and the frames are written there.  A frame whose output file exists is skipped.  `batch` frames go through
-    one fused launch; PNG decode and encode run on `workers` threads (default: the CPUs this process may use, at most 16)."""
+    one fused launch; PNG decode and encode run on `workers` threads (default: the CPUs this process may use, at most 16).
+    encoder='pillow' (the default) writes the files with Pillow from a host copy of the rectified frames; encoder='device' keeps them
+    on the device, where clslam_hip.png turns the batch into file bytes behind the fused launch on the same stream (literal-only
+    deflate: larger files, the same pixels), and the threads only write those bytes."""
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
+    if encoder not in ('pillow', 'device'):
+        raise ValueError(f"undistort_images: encoder must be 'pillow' or 'device', got {encoder!r}")
     batch = max(int(batch), 1)
     workers = _default_workers() if workers is None else max(int(workers), 1)
     if data_path_out is None:
@@ -234,6 +241,10 @@ def undistort_images(data_path_in, models_path, data_path_out=None, batch: int =
     def encode(path, array):
         Image.fromarray(array).save(path)
 
+    def write(path, data):
+        with open(path, 'wb') as f:
+            f.write(data)
+
     with ThreadPoolExecutor(max_workers=workers, thread_name_prefix='clslam-robotcar-png') as pool:
         chunks = [todo[i:i + batch] for i in range(0, len(todo), batch)]
         decoding = [pool.submit(decode, f) for f in chunks[0]] if chunks else []
@@ -241,9 +252,15 @@ def undistort_images(data_path_in, models_path, data_path_out=None, batch: int =
         for ci, chunk in enumerate(chunks):
             raw = np.stack([f.result() for f in decoding])
             decoding = [pool.submit(decode, f) for f in chunks[ci + 1]] if ci + 1 < len(chunks) else []
-            rgb = model.rectify(raw)                                     # upload, one launch, download
+            if encoder == 'device':
+                blobs = png.encode_batch(model.rectify(raw, on_device=True))          # upload, launches, download of the files
+            else:
+                rgb = model.rectify(raw)                                 # upload, one launch, download
             while len(encoding) > 2 * workers:                           # the encoder is the slow stage: keep every thread fed,
                 encoding.pop(0).result()                                 # and bound the rectified frames waiting for one
-            encoding += [pool.submit(encode, Path(data_path_out) / f.name, rgb[i]) for i, f in enumerate(chunk)]
+            if encoder == 'device':
+                encoding += [pool.submit(write, Path(data_path_out) / f.name, blobs[i]) for i, f in enumerate(chunk)]
+            else:
+                encoding += [pool.submit(encode, Path(data_path_out) / f.name, rgb[i]) for i, f in enumerate(chunk)]
         for f in encoding:
             f.result()

@@ -46,7 +46,9 @@ extern "C" {
  * 110 = clslam_pose_pair_error, clslam_traj_metrics* added; 111 = clslam_resize_level_u8, clslam_ring_gather added (online ingest).
  * 112 = clslam_pair_loss added (predict_from_images); 113 = clslam_pcl_voxel_* added (voxel-grid downsampling of a cloud).
  * 114 = clslam_demosaic_bilinear, clslam_undistort_lut, clslam_robotcar_rectify added (RobotCar raw frames).
- * Bindings check it before the first call.                                                                                    */
+ * 114 also carries clslam_png_* (PNG encoding): purely additive -- no struct, no existing signature changes -- so the number stays;
+ * a binding that needs them reports a library built before them by the name of the missing entry point.
+ * Bindings check it before the first call.                                                                                  */
 #define CLSLAM_ABI_VERSION 114
 int clslam_version(void);
 const char* clslam_last_error(void);
@@ -721,6 +723,50 @@ int clslam_demosaic_bilinear(const unsigned char* cfa, double* out, int n, int h
 int clslam_undistort_lut(const void* image, const double* lut, void* out, int n, int h, int w, int c, int is_f64, void* stream);
 int clslam_robotcar_rectify(const unsigned char* cfa, const double* lut, unsigned char* out, int n, int h, int w, int pattern,
                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * PNG encoding on the device (csrc/png_encode.hip): n images of one size, uint8, contiguous, (n,h,w) (channels = 1, colour type 0)
+ * or (n,h,w,3) (channels = 3, colour type 2), bit depth 8, bpp = channels -> one complete PNG file per image in a caller-allocated
+ * device buffer, plus each file's length.  Nothing synchronises; only the n lengths and then the bytes need to reach the host.
+ *
+ * FILTER (clslam_png_filter).  filtered (n rows of filtered_stride bytes): image i is h scanlines of 1 + w*bpp bytes, the filter type
+ * and then the filtered bytes (RFC 2083 section 6: None, Sub, Up, Average, Paeth; the row above row 0 and the bytes left of the first
+ * pixel are 0).  filter = CLSLAM_PNG_FILTER_ADAPTIVE keeps, per row, the type with the smallest score sum(min(b, 256 - b)) over the
+ * row's filtered bytes, ties to the LOWEST type; filter = 0..4 uses that type on every row.  One launch, one workgroup per row.
+ *
+ * DEFLATE (clslam_png_deflate) wraps such a filtered stream.  There is no LZ77 matching: the stream is cut into blocks of
+ * S = CLSLAM_PNG_BLOCK = 16384 bytes (the last one shorter), and each block is either a DYNAMIC block of literals only -- the
+ * length-limited (<= 15 bits) canonical Huffman code of its own histogram of the 256 literals + end-of-block: the optimal code
+ * whenever an optimal code of depth <= 15 exists (the two-queue construction prefers leaves on ties, which gives the optimal tree
+ * of least depth), else a complete code obtained by moving leaves down; HLIT = 257 codes, HDIST = 1 distance code of length 0
+ * (= "literals only"), HCLEN = 19 with the sixteen code-length symbols 0..15 at 4 bits each and no run-length symbols, i.e. a
+ * header of 1106 bits -- or a STORED block, whenever the dynamic form would not end before the stored form would at the block's
+ * actual bit position.  The last block carries BFINAL.  S: 16 KiB keeps the block's histogram, code table and packed bits in
+ * LDS, gives a 960x1280x3 frame 226 independent workgroups, and holds the header at under 1 % of the block.
+ *
+ * FILE.  signature, IHDR, ONE IDAT = zlib header 78 01 + the deflate stream + Adler-32 of the filtered stream, IEND.  Adler-32 is
+ * combined from per-block (a, b) pairs, the IDAT CRC-32 from per-block remainders multiplied by x^(8 * bytes that follow) mod P.
+ *
+ * clslam_png_bound(h, w, channels): the worst-case file size.  F = h * (1 + w*channels) filtered bytes in B = ceil(F / S) blocks;
+ * a block never ends later than its stored form would, and a stored form that starts at or before byte boundary b ends at or before
+ * b + 5 + len (3 header bits and padding <= 1 byte further, LEN + NLEN 4 bytes, len bytes of data), so by induction the stream
+ * is at most F + 5 B bytes; + 2 (zlib header) + 4 (Adler-32) + 57 (signature 8, IHDR 25, IDAT 12, IEND 12): F + 5 B + 63.  0 for
+ * a geometry the library does not take.  out holds n files, file i at out + i * out_stride; out_stride >= the bound, a multiple of
+ * 4, out 4-byte aligned (bits are added into zeroed 32-bit words); bytes of a row past lengths[i] are zero or untouched.
+ * clslam_png_scratch(n, h, w, channels): bytes of 16-byte-aligned device scratch clslam_png_encode needs (clslam_png_deflate
+ * needs no more).  filtered: 16-byte aligned, filtered_stride a multiple of 16 and >= F.
+ *
+ * h, w >= 1, channels 1 or 3, F <= 2^27, n <= 65535 (n = 0 is a no-op).  Bad arguments are refused before any launch.          */
+#define CLSLAM_PNG_BLOCK 16384
+#define CLSLAM_PNG_FILTER_ADAPTIVE (-1)
+long long clslam_png_bound(int h, int w, int channels);
+long long clslam_png_scratch(int n, int h, int w, int channels);
+int clslam_png_filter(const unsigned char* image, unsigned char* filtered, long long filtered_stride, int n, int h, int w, int channels,
+                      int filter, void* stream);
+int clslam_png_deflate(const unsigned char* filtered, long long filtered_stride, unsigned char* out, long long out_stride, int* lengths,
+                       void* scratch, long long scratch_bytes, int n, int h, int w, int channels, void* stream);
+int clslam_png_encode(const unsigned char* image, unsigned char* out, long long out_stride, int* lengths, void* scratch,
+                      long long scratch_bytes, int n, int h, int w, int channels, int filter, void* stream);
 
 #ifdef __cplusplus
 }
