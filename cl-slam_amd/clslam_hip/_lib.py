@@ -21,6 +21,9 @@ PNG_FILTERS = {'adaptive': PNG_FILTER_ADAPTIVE, 'none': 0, 'sub': 1, 'up': 2, 'a
 DEPTH_EVAL_MEDIAN_SCALING, DEPTH_EVAL_FROM_DISP, DEPTH_EVAL_NO_MAX = 1, 2, 4
 TRAJ_MAX_POSES = 1 << 20             # include/clslam_hip.h CLSLAM_TRAJ_MAX_POSES
 BAYER_PATTERNS = {'rggb': 0, 'bggr': 1, 'grbg': 2, 'gbrg': 3}      # CLSLAM_BAYER_*
+VIZ_MAX_ROWS, VIZ_MAX_W = 4, 8192                                    # CLSLAM_VIZ_MAX_ROWS, CLSLAM_VIZ_MAX_W
+VIZ_ROW_CHW_F32, VIZ_ROW_HWC_F32, VIZ_ROW_HWC_F64, VIZ_ROW_HWC_U8, VIZ_ROW_CMAP, VIZ_ROW_TRAJ = 0, 1, 2, 3, 4, 5     # CLSLAM_VIZ_ROW_*
+VIZ_CMAPS = {'magma': 0, 'magma_r': 1}                               # CLSLAM_VIZ_CMAP_*
 
 fptr = C.c_void_p
 i32 = C.c_int32
@@ -66,6 +69,11 @@ class RingGatherDesc(C.Structure):
     _fields_ = [('rgb', fptr * STORE_MAX_PLANES), ('aug', fptr * STORE_MAX_PLANES), ('offset', C.c_int64 * STORE_MAX_PLANES),
                 ('h', i32 * STORE_MAX_PLANES), ('w', i32 * STORE_MAX_PLANES), ('slot', i32 * STORE_MAX_PLANES),
                 ('n_frames', i32), ('n_levels', i32), ('capacity', i32), ('slot_bytes', C.c_int64)]
+
+
+class VizRow(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('range', fptr), ('gt_xz', fptr), ('pred_xz', fptr), ('src_stride', C.c_longlong),
+                ('xlim', C.c_double * 2), ('ylim', C.c_double * 2), ('kind', i32), ('cmap', i32), ('n_gt', i32), ('n_pred', i32)]
 
 
 # name -> argtypes (restype is always int unless listed in _RESTYPES)
@@ -192,11 +200,14 @@ _SIGNATURES = {
                            C.c_void_p],
     'clslam_png_encode': [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, i32, i32, i32, i32, i32,
                           C.c_void_p],
+    'clslam_viz_range': [fptr, fptr, C.c_void_p, C.c_void_p, C.c_longlong, i32, C.c_longlong, C.c_double, C.c_void_p],
+    'clslam_viz_compose': [C.POINTER(VizRow), i32, C.c_void_p, C.c_longlong, C.c_longlong, i32, i32, i32, i32, C.c_void_p],
 }
 _RESTYPES = {'clslam_last_error': C.c_char_p, 'clslam_last_error_string': C.c_char_p, 'clslam_build_id': C.c_char_p}
 ABI_VERSION = 114          # include/clslam_hip.h CLSLAM_ABI_VERSION: struct layouts / pointer types this binding was written for
 _SIZE_FNS = {'clslam_wino_weight_size': [i32, i32], 'clslam_pcl_voxel_scratch': [C.c_longlong]}      # return size_t
-_I64_FNS = {'clslam_png_bound': [i32, i32, i32], 'clslam_png_scratch': [i32, i32, i32, i32]}       # return long long
+_I64_FNS = {'clslam_png_bound': [i32, i32, i32], 'clslam_png_scratch': [i32, i32, i32, i32],
+            'clslam_viz_range_scratch': [i32]}                                                      # return long long
 _PTR_FNS = {'clslam_handoff_event_create': []}             # return void*
 _VOID_FNS = {'clslam_handoff_event_destroy': [C.c_void_p]}
 
@@ -207,7 +218,7 @@ class ClslamError(RuntimeError):
 
 def bind_entry_points(cdll, path='the library') -> None:
     """Set restype / argtypes of every entry point of include/clslam_hip.h on `cdll`.  The ABI number says the descriptors' layout;
-    entry points added without changing it (clslam_png_*, ABI 114) are missing from a library built before them: that is a
+    entry points added without changing it (clslam_png_*, clslam_viz_*, ABI 114) are missing from a library built before them: that is a
     ClslamError naming the entry point and the remedy, not an AttributeError."""
     tables = [(_RESTYPES, None), (_SIZE_FNS, C.c_size_t), (_I64_FNS, C.c_longlong), (_PTR_FNS, C.c_void_p), (_VOID_FNS, None),
               (_SIGNATURES, C.c_int)]

@@ -1246,3 +1246,108 @@ def png_encode(images, filter=_lib.PNG_FILTER_ADAPTIVE, out=None):
     _lib.get_lib().call('clslam_png_encode', _pa(images, torch.uint8), _pa(out, torch.uint8), out.shape[1], _pa(lengths, torch.int32),
                         _pa(scratch, torch.uint8), nbytes, N, H, W, Cn, code, _stream(images))
     return out, lengths
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Frame panels (csrc/viz.hip; the user-facing names are in clslam_hip/viz.py)
+_VIZ_IMAGE_KINDS = {torch.float32: _lib.VIZ_ROW_HWC_F32, torch.float64: _lib.VIZ_ROW_HWC_F64, torch.uint8: _lib.VIZ_ROW_HWC_U8}
+
+
+def viz_range(planes, q: float = 95.0):
+    """planes (N,H,W) fp32 -> (range (N,2) fp32 = {vmin, vmax}, count (N,) int32) on the device: the smallest finite value, the
+    q-th percentile of the finite values by the float64 rule of include/clslam_hip.h, their number.  Nothing synchronises."""
+    fn = 'viz_range'
+    if not isinstance(planes, torch.Tensor) or planes.dtype is not torch.float32 or planes.dim() != 3 or planes.shape[0] == 0 \
+            or planes.shape[1] * planes.shape[2] == 0:
+        raise _lib.ClslamError(f'{fn}: planes must be a non-empty (N,H,W) float32 tensor, got '
+                               f'{(tuple(planes.shape), planes.dtype) if isinstance(planes, torch.Tensor) else type(planes).__name__}')
+    q = float(q)
+    if not 0.0 <= q <= 100.0:
+        raise _lib.ClslamError(f'{fn}: q must lie in [0, 100], got {q}')
+    N, npx = planes.shape[0], planes.shape[1] * planes.shape[2]
+    rng = torch.empty((N, 2), dtype=torch.float32, device=planes.device)
+    count = torch.empty((N,), dtype=torch.int32, device=planes.device)
+    for n0 in range(0, N, 65535):
+        n = min(65535, N - n0)
+        nbytes = int(_query('clslam_viz_range_scratch', n))
+        scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=planes.device)
+        _lib.get_lib().call('clslam_viz_range', _pa(planes[n0:n0 + n], torch.float32), _pa(rng[n0:n0 + n], torch.float32),
+                            _pa(count[n0:n0 + n], torch.int32), _pa(scratch, torch.int64), nbytes, n, npx, q, _stream(planes))
+    return rng, count
+
+
+def viz_image_row(image, chw: bool = False):
+    """a row of a panel from an image: (N,3,H,W) fp32 in [0,1] with chw, else (N,H,W,3) fp32 / fp64 / uint8"""
+    return ('image', image, bool(chw))
+
+
+def viz_cmap_row(planes, rng, cmap='magma_r'):
+    """a row of a panel from planes (N,H,W) fp32 through the colour map, rng (N,2) fp32 {vmin, vmax} on the device"""
+    return ('cmap', planes, rng, cmap)
+
+
+def viz_traj_row(gt_xz, pred_xz, xlim=(-400.0, 15.0), ylim=(-60.0, 160.0)):
+    """a white row with the polylines gt_xz (Ng,2) and pred_xz (Np,2), fp64 on the device (either may be None or empty)"""
+    return ('traj', gt_xz, pred_xz, tuple(xlim), tuple(ylim))
+
+
+def viz_compose(rows, n: int, h: int, w: int, dst=None, row0: int = 0):
+    """rows: up to four of viz_image_row / viz_cmap_row / viz_traj_row -> dst (n, >= row0 + len(rows) * h, >= w, 3) uint8: row r
+    fills the pixel rows [row0 + r*h, row0 + (r+1)*h) x [0, w) of every image, ONE launch, nothing else of dst is written.  dst
+    may be a view with wider rows (stride(1) >= 3 * w, pixels and channels dense); None: a new (n, len(rows) * h, w, 3)."""
+    fn = 'viz_compose'
+    lib = _lib.get_lib()
+    n, h, w, row0 = int(n), int(h), int(w), int(row0)
+    if not 1 <= len(rows) <= _lib.VIZ_MAX_ROWS:
+        raise _lib.ClslamError(f'{fn}: 1..{_lib.VIZ_MAX_ROWS} rows, got {len(rows)}')
+    if n < 1 or h < 1 or not 1 <= w <= _lib.VIZ_MAX_W:
+        raise _lib.ClslamError(f'{fn}: n >= 1 images of h >= 1, 1 <= w <= {_lib.VIZ_MAX_W}, got n={n} h={h} w={w}')
+    descs = (_lib.VizRow * len(rows))()
+    keep = []                                                  # the tensors behind the descriptors' pointers
+    for d, row in zip(descs, rows):
+        if row[0] == 'image':
+            _, t, chw = row
+            shape = (n, 3, h, w) if chw else (n, h, w, 3)
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or (t.dtype is not torch.float32 if chw else t.dtype not in _VIZ_IMAGE_KINDS):
+                raise _lib.ClslamError(f'{fn}: an image row must be {shape} {"float32" if chw else "float32 / float64 / uint8"}, got '
+                                       f'{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}')
+            d.kind = _lib.VIZ_ROW_CHW_F32 if chw else _VIZ_IMAGE_KINDS[t.dtype]
+            d.src, d.src_stride = _pa(t, t.dtype), 3 * h * w
+            keep.append(t)
+        elif row[0] == 'cmap':
+            _, t, rng, cmap = row
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (n, h, w) or t.dtype is not torch.float32:
+                raise _lib.ClslamError(f'{fn}: a colour row must be ({n},{h},{w}) float32, got '
+                                       f'{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}')
+            if not isinstance(rng, torch.Tensor) or tuple(rng.shape) != (n, 2) or rng.dtype is not torch.float32:
+                raise _lib.ClslamError(f'{fn}: the range of a colour row must be ({n},2) float32')
+            if cmap not in _lib.VIZ_CMAPS:
+                raise _lib.ClslamError(f'{fn}: cmap must be one of {sorted(_lib.VIZ_CMAPS)}, got {cmap!r}')
+            d.kind, d.cmap = _lib.VIZ_ROW_CMAP, _lib.VIZ_CMAPS[cmap]
+            d.src, d.src_stride, d.range = _pa(t, torch.float32), h * w, _pa(rng, torch.float32)
+            keep += [t, rng]
+        elif row[0] == 'traj':
+            _, gt, pred, xlim, ylim = row
+            d.kind = _lib.VIZ_ROW_TRAJ
+            d.xlim[0], d.xlim[1], d.ylim[0], d.ylim[1] = float(xlim[0]), float(xlim[1]), float(ylim[0]), float(ylim[1])
+            for name, line in (('gt_xz', gt), ('pred_xz', pred)):
+                if line is None or (isinstance(line, torch.Tensor) and line.numel() == 0):
+                    continue
+                if not isinstance(line, torch.Tensor) or line.dim() != 2 or line.shape[1] != 2 or line.dtype is not torch.float64:
+                    raise _lib.ClslamError(f'{fn}: {name} must be an (N,2) float64 tensor')
+                setattr(d, name, _pd(line))
+                setattr(d, 'n_gt' if name == 'gt_xz' else 'n_pred', line.shape[0])
+                keep.append(line)
+        else:
+            raise _lib.ClslamError(f'{fn}: unknown row {row[0]!r}')
+    device = keep[0].device if keep else torch.device('cuda', torch.cuda.current_device()) if lib.is_device else torch.device('cpu')
+    if dst is None:
+        dst = torch.empty((n, row0 + len(rows) * h, w, 3), dtype=torch.uint8, device=device)
+    if not isinstance(dst, torch.Tensor) or dst.dtype is not torch.uint8 or dst.dim() != 4 or dst.shape[0] != n or dst.shape[3] != 3 \
+            or dst.shape[1] < row0 + len(rows) * h or dst.shape[2] < w or row0 < 0 or dst.stride(3) != 1 or dst.stride(2) != 3 \
+            or dst.stride(1) < 3 * w or dst.device.type != lib.device_type:
+        raise _lib.ClslamError(f'{fn}: dst must be ({n}, >= {row0 + len(rows) * h}, >= {w}, 3) uint8 on {lib.device_type} with dense '
+                               f'pixels, got {(tuple(dst.shape), dst.dtype, dst.stride()) if isinstance(dst, torch.Tensor) else type(dst).__name__}')
+    lib.call('clslam_viz_compose', descs, len(rows), dst.data_ptr(), dst.stride(0) if n > 1 else 0, dst.stride(1), row0, n, h, w,
+             _stream(dst))
+    return dst

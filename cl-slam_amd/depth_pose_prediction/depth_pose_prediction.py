@@ -13,8 +13,10 @@ min_depth, max_depth, log_path``; the caller's input dict is moved to the device
 What is different by design: all arithmetic runs in ``clslam_hip.engine.Engine`` (no autograd, no
 torch.nn compute); there is NO CPU path -- constructing the predictor without a GPU / without
 libclslam_hip.so raises.  Provided from the evaluation side: ``compute_depth_error`` (dpp.py:344-468, the metrics on the device:
-clslam_hip/depth_eval.py), ``predict_from_image`` (dpp.py:538-554) and ``predict_from_images`` (dpp.py:556-626).  Offline
-pre-training and plotting (dpp.py:219-289, 829-904, 1197-1267) are outside the accelerated path and not provided.
+clslam_hip/depth_eval.py), ``predict_from_image`` (dpp.py:538-554) and ``predict_from_images`` (dpp.py:556-626).  From the
+logging side: ``save_prediction`` (dpp.py:1197-1244) as panels formed and PNG-encoded on the device (clslam_hip/viz.py: no
+matplotlib, no titles, no wandb image; ``validate`` does not call it yet).  Offline pre-training (dpp.py:219-289, 829-904) and
+wandb logging (dpp.py:1246-1267) are outside the accelerated path and not provided.
 """
 import math
 import shutil
@@ -778,6 +780,28 @@ class DepthPosePrediction:
             transformation = transformation.squeeze().cpu().detach().numpy()
             cov_matrix = cov_matrix.cpu().detach().numpy()
         return transformation, cov_matrix
+
+    # ============================================================
+    # Logging
+
+    def save_prediction(self, inputs: Dict[Any, Tensor], outputs: Dict[Any, Tensor]) -> None:
+        """dpp.py:1197-1244 without matplotlib: for every sample of the batch a two-row panel, inputs['rgb', 0, 0][i] over
+        outputs['depth', 0][i] as magma_r from its smallest value to its 95th percentile (clslam_hip/viz.py), written to
+        <log_path>/prediction/val_depth_{epoch:03}/{index:05}.png.  The whole batch is one range computation, one composing
+        launch and one png.encode_batch; the depth planes never reach the host.  No titles (the vmax of a title is
+        viz.depth_range's) and no wandb image."""
+        from clslam_hip import ops, png
+        save_folder = Path(self.log_path) / 'prediction' / f'val_depth_{self.epoch:03}'
+        save_folder.mkdir(parents=True, exist_ok=True)
+        rgb = inputs['rgb', 0, 0].to(self.device, torch.float32).contiguous()
+        depth = outputs['depth', 0].to(self.device, torch.float32)
+        N, _, H, W = rgb.shape
+        planes = depth.reshape(N, H, W).contiguous()
+        rng, _ = ops.viz_range(planes, 95.0)
+        panels = ops.viz_compose([ops.viz_image_row(rgb, chw=True), ops.viz_cmap_row(planes, rng, 'magma_r')], N, H, W)
+        for index, data in zip(inputs['index'], png.encode_batch(panels)):
+            with open(save_folder / f'{int(index):05}.png', 'wb') as f:
+                f.write(data)
 
     # ============================================================
     # Save / load (dpp.py:669-749): same files, same keys

@@ -47,7 +47,8 @@ extern "C" {
  * 112 = clslam_pair_loss added (predict_from_images); 113 = clslam_pcl_voxel_* added (voxel-grid downsampling of a cloud).
  * 114 = clslam_demosaic_bilinear, clslam_undistort_lut, clslam_robotcar_rectify added (RobotCar raw frames).
  * 114 also carries clslam_png_* (PNG encoding): purely additive -- no struct, no existing signature changes -- so the number stays;
- * a binding that needs them reports a library built before them by the name of the missing entry point.
+ * a binding that needs them reports a library built before them by the name of the missing entry point.  The same holds for
+ * clslam_viz_* (frame panels): one new descriptor struct of their own, nothing that exists changes.
  * Bindings check it before the first call.                                                                                  */
 #define CLSLAM_ABI_VERSION 114
 int clslam_version(void);
@@ -767,6 +768,69 @@ int clslam_png_deflate(const unsigned char* filtered, long long filtered_stride,
                        void* scratch, long long scratch_bytes, int n, int h, int w, int channels, void* stream);
 int clslam_png_encode(const unsigned char* image, unsigned char* out, long long out_stride, int* lengths, void* scratch,
                       long long scratch_bytes, int n, int h, int w, int channels, int filter, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Frame panels on the device (csrc/viz.hip): what slam/utils.py:85-121 generate_figure and dpp.py:1197-1244 save_prediction draw
+ * with matplotlib -- the frame, the depth plane as magma_r up to its 95th percentile, the projected map, the x/z trajectory -- as
+ * uint8 RGB pixels, without text, axes or legend.  Nothing synchronises and nothing is read back.
+ *
+ * RANGE (clslam_viz_range; replaces utils.py:100 / dpp.py:1224 `vmax = np.percentile(depth, 95)` and imshow's implicit vmin).
+ * planes: n contiguous fp32 planes of npx values.  Only FINITE values take part, m of them (np.percentile would answer NaN).
+ * They are ordered by the monotone 32-bit key of the float (sign bit flipped, or all bits flipped for a negative value; -0 below
+ * +0), a[0..m-1].  range[2i] = vmin = a[0].  range[2i+1] = vmax: pos = q / 100 * (m - 1) in fp64, k = floor(pos), g = pos - k,
+ * vmax = (float)((double)a[k] + ((double)a[min(k+1, m-1)] - (double)a[k]) * g), every fp64 operation rounded, no contraction.
+ * The three order statistics are exact (a radix select of 8 bits per pass over the keys).  count[i] = m.  m = 0: vmin = vmax = NaN.
+ * 0 <= q <= 100.  Launches: a memset, the digit-0 histogram, three selecting passes, one finishing block per plane.
+ * clslam_viz_range_scratch(n): bytes of 8-byte-aligned device scratch for n planes (0: n out of range).
+ *
+ * COMPOSE (clslam_viz_compose).  One launch writes n_rows rows of h x w pixels, row r into the pixel rows
+ * [row0 + r*h, row0 + (r+1)*h) and the columns [0, w) of image i of dst: byte (y, x, c) of image i is at
+ * dst + i * dst_image_stride + y * dst_row_stride + 3 * x + c; nothing else of dst is written.  Row kinds:
+ *   CHW_F32  (n,3,h,w) fp32 in [0,1]    HWC_F32 / HWC_F64 / HWC_U8  (n,h,w,3)      src_stride: elements between images.
+ *            float -> byte: trunc(clamp(x, 0, 1) * 255 + 0.5) in the source's precision, each operation rounded; NaN -> 0
+ *            (recovers b from (float)(b / 255.0), the frame store's rule); uint8 is copied.
+ *   CMAP     (n,h,w) fp32 through a 256-entry table, matplotlib's arithmetic as Normalize and Colormap carry it out on a float32
+ *            plane: r = (float)((double)x - vmin), t = (float)((double)r / ((double)vmax - vmin)) -- the divisor is the exact
+ *            difference, the division the correctly rounded IEEE one -- xa = t * 256 in fp32; xa < 0 -> entry 0; xa >= 256 -> entry 255 (256 itself, and the
+ *            "over" colour); else entry trunc(xa); x or xa NaN -> (0,0,0) (imshow's masked pixel); vmin == vmax -> entry 0 for
+ *            every x that is not NaN (Normalize's rule).  +inf -> entry 255, -inf -> entry 0.  range: (n,2) {vmin, vmax} on the
+ *            device, e.g. clslam_viz_range's.  cmap: MAGMA, or MAGMA_R = the same table read backwards;
+ *            the table is matplotlib's magma lut * 255 truncated, [0 0 3] .. [251 252 191].
+ *   TRAJ     a white row with two polylines of (x, y) fp64 vertices, 1 pixel wide, gt (31,119,180) and over it pred (255,127,14)
+ *            (utils.py:113-116).  Vertex -> pixel in fp64: u = floor((x - xlim[0]) / (xlim[1] - xlim[0]) * w),
+ *            v = floor((ylim[1] - y) / (ylim[1] - ylim[0]) * h), clamped to +-2^30, then 64-bit integers.  A segment (u0,v0)-(u1,v1)
+ *            with n = max(|du|, |dv|) sets, for k = 0..n, the pixel (u0 + floor((2 k du + n) / (2 n)), v0 + floor((2 k dv + n) /
+ *            (2 n))) (floor division; n = 0: that pixel); pixels outside the row are dropped.  A segment with a non-finite
+ *            vertex is skipped, one vertex draws one pixel, none draws nothing.  k is clipped to the row before anything is
+ *            drawn: the work per segment is bounded by the row's size, not by its length -- per BLOCK: every block of the row (a
+ *            band of min(8, 8192 / w) pixel rows) walks all segments, so a row costs (h / band) * segments clip tests; meant
+ *            for rows of a few hundred pixel rows.  The same polylines go into every image i.
+ * 1 <= n_rows <= CLSLAM_VIZ_MAX_ROWS, n <= 65535 (n = 0 is a no-op), 1 <= h <= 2^24, 1 <= w <= CLSLAM_VIZ_MAX_W, h * w <= 2^30,
+ * n_gt, n_pred <= 2^24, xlim / ylim finite with distinct ends.  Bad arguments are refused before any launch.                  */
+#define CLSLAM_VIZ_MAX_ROWS 4
+#define CLSLAM_VIZ_MAX_W 8192
+#define CLSLAM_VIZ_ROW_CHW_F32 0
+#define CLSLAM_VIZ_ROW_HWC_F32 1
+#define CLSLAM_VIZ_ROW_HWC_F64 2
+#define CLSLAM_VIZ_ROW_HWC_U8 3
+#define CLSLAM_VIZ_ROW_CMAP 4
+#define CLSLAM_VIZ_ROW_TRAJ 5
+#define CLSLAM_VIZ_CMAP_MAGMA 0
+#define CLSLAM_VIZ_CMAP_MAGMA_R 1
+typedef struct clslam_viz_row {
+    const void* src;         /* image / plane rows; unused by TRAJ */
+    const float* range;      /* CMAP: (n,2) vmin, vmax */
+    const double* gt_xz;     /* TRAJ: (n_gt,2), may be null when n_gt = 0 */
+    const double* pred_xz;   /* TRAJ: (n_pred,2) */
+    long long src_stride;
+    double xlim[2], ylim[2]; /* TRAJ */
+    int kind, cmap, n_gt, n_pred;
+} clslam_viz_row;
+long long clslam_viz_range_scratch(int n);
+int clslam_viz_range(const float* planes, float* range, int* count, void* scratch, long long scratch_bytes, int n, long long npx,
+                     double q, void* stream);
+int clslam_viz_compose(const clslam_viz_row* rows, int n_rows, unsigned char* dst, long long dst_image_stride,
+                       long long dst_row_stride, int row0, int n, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }
