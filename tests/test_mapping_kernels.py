@@ -160,6 +160,105 @@ def test_backproject_edges(backend):
     assert (out[int(off[-1]):] == -7.0).all()                                        # nothing written past the kept rows
 
 
+# ---- backproject: the one-block scan over more chunks than it has threads -----------------------------------------------------------
+SCAN_PLANES = [(256, 1, 1, 256), (257, 1, 1, 257), (129, 1, 1025, 258), (86, 1, 2049, 258), (3, 192, 640, 360)]
+SCAN_THR = 20.3
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_planes(n, h, w):
+    """n planes whose points are exact in fp32, so that float64 and the kernel agree to the bit.  inv_K of image i: focal length
+    2^s with 2^s >= max(h, w), a principal point (cx, cy) of its own inside the plane; depths are eighths.  (px - cx) 2^-s has 12
+    bits at most and |.| <= 1, a depth below 64 nine: the products are exact, and z = depth.  Image i is, by i % 4: mixed (depth
+    1 .. 40: SCAN_THR keeps the pixels with depth * sqrt(u^2 + v^2 + 1) < 20.3, so pixels inside a chunk part ways), near (depth
+    below 8: all kept), far (depth from 24: none kept), mixed."""
+    rng = np.random.default_rng(1000 * n + h * w)
+    s = int(np.ceil(np.log2(max(h, w, 2))))
+    inv_K = np.zeros((n, 4, 4), np.float32)
+    inv_K[:, 0, 0] = inv_K[:, 1, 1] = 2.0 ** -s
+    inv_K[:, 0, 2] = -rng.integers(0, w, n) * 2.0 ** -s
+    inv_K[:, 1, 2] = -rng.integers(0, h, n) * 2.0 ** -s
+    inv_K[:, 2, 2] = inv_K[:, 3, 3] = 1
+    kind = np.arange(n) % 4
+    lo = np.where(kind == 1, 8, np.where(kind == 2, 192, 8))[:, None, None, None]
+    hi = np.where(kind == 1, 64, np.where(kind == 2, 512, 320))[:, None, None, None]
+    depth = (rng.integers(lo, hi, (n, 1, h, w)) / 8.0).astype(np.float32)
+    out = {'depth': depth, 'inv_K': inv_K, 'image': rng.random((n, 3, h, w)).astype(np.float32)}
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_reference(n, h, w, thr):
+    """-> (rows (sum M,6) float32, offsets (n+1,), kept per chunk (n, chunks), pixels per chunk (chunks,)); the premises asserted:
+    float64 coordinates that fp32 holds exactly, and no distance within 2^-21 of the threshold"""
+    s = _exact_planes(n, h, w)
+    rows, kept = [], []
+    starts = np.arange(0, h * w, 1024)
+    for f in range(n):
+        r = R.backproject(s['depth'][f, 0], s['inv_K'][f], s['image'][f], thr)
+        assert np.array_equal(r['cam'].astype(np.float32).astype(np.float64), r['cam'])
+        assert not R.threshold_band(r['norm'], r['threshold']).any()
+        rows.append(r['points'].astype(np.float32))
+        kept.append(np.add.reduceat(r['keep'].astype(np.int64), starts))
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    return np.concatenate(rows), offsets, np.stack(kept), np.diff(np.concatenate([starts, [h * w]]))
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+@pytest.mark.parametrize('n,h,w,G', SCAN_PLANES, ids=[f'{n}x{h}x{w}' for n, h, w, _ in SCAN_PLANES])
+def test_backproject_scan_beyond_one_chunk_per_thread(backend, n, h, w, G):
+    """pcl_bp_scan_kernel: one block of 256 threads, thread t scans `per = ceil(G / 256)` chunk counts from `lo = min(t * per, G)`
+    and writes offsets[g / chunks] where `g % chunks == 0` inside its loop.
+      256 x (1x1)     G = 256  per == 1, every thread exactly one chunk
+      257 x (1x1)     G = 257  per == 2, the threads from 129 on empty, every chunk an image of its own
+      129 x (1x1025)  G = 258  chunks == 2: a thread's pair is one whole image
+      86 x (1x2049)   G = 258  chunks == 3: image boundaries fall inside a thread's range
+      3 x (192x640)   G = 360  the workload's own shape
+    Rows bitwise and offsets exact against mapping_reference (exact planes: _exact_planes), with an infinite threshold (counts
+    known without looking) and with one that keeps about half; there, chunks that keep nothing and chunks that keep everything,
+    and whole images that keep nothing.  Measured, seconds per case in the order above, both thresholds and the reference together,
+    CPU emulator | MI355X: 0.06 | 0.01, 0.07 | 0.01, 0.08 | 0.01, 0.08 | 0.05, 0.18 | 0.04."""
+    dev = use_backend(backend)
+    chunks = -(-h * w // 1024)
+    assert n * chunks == G and -(-G // 256) == (1 if G <= 256 else 2)
+    s = _exact_planes(n, h, w)
+    for thr in (np.inf, SCAN_THR):
+        rows, offsets, kept, size = _exact_reference(n, h, w, thr)
+        if np.isinf(thr):
+            assert np.array_equal(offsets, np.arange(n + 1) * h * w)
+        else:
+            share = offsets[-1] / (n * h * w)
+            assert 0.25 <= share <= 0.75, share
+            assert (kept == 0).any() and (kept == size).any() and (np.diff(offsets) == 0).any()
+            if h * w > 1:
+                assert ((kept > 0) & (kept < size)).any()                                # the threshold parts pixels inside a chunk
+        pts, off = _backproject(dev, s, thr)
+        print(f'[backproject scan {backend}] {n} x ({h}x{w}) thr {thr}: G = {G}, kept {int(offsets[-1])} of {n * h * w}, '
+              f'chunks that keep nothing {int((kept == 0).sum())}, everything {int((kept == size).sum())}')
+        assert np.array_equal(off, offsets)
+        assert pts.shape == rows.shape and np.array_equal(_bits(pts), _bits(rows))
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+def test_backproject_scan_leaves_the_rest_of_the_buffer(backend):
+    """pcl_bp_scan_kernel at `per == 2` (G = 258, 86 planes of 1x2049) with narrow=False: the rows up to offsets[-1] are the
+    reference's and the rows past it keep the NaN pattern the buffer was filled with, bit for bit.  Measured: 0.04 s on the CPU
+    emulator, under 0.005 s on the MI355X (the reference is the one of the case above)."""
+    dev = use_backend(backend)
+    n, h, w = 86, 1, 2049
+    s = _exact_planes(n, h, w)
+    rows, offsets, _, _ = _exact_reference(n, h, w, SCAN_THR)
+    assert 0 < offsets[-1] < n * h * w - 1024
+    fill = np.uint32(0x7fc0beef)
+    out = torch.from_numpy(np.full((n * h * w + 5, 6), fill, np.uint32).view(np.float32)).to(dev)
+    full, off = ops.pcl_backproject(_t(s['depth'], dev), _t(s['inv_K'], dev), _t(s['image'], dev), SCAN_THR, out=out, narrow=False)
+    assert full.data_ptr() == out.data_ptr() and full.shape == out.shape and np.array_equal(off.cpu().numpy(), offsets)
+    got = out.cpu().numpy().view(np.uint32)
+    assert np.array_equal(got[:offsets[-1]], _bits(rows)) and (got[offsets[-1]:] == fill).all()
+
+
 # ---- transform ----------------------------------------------------------------------------------------------------------------
 def _metre_poses(n, seed=1):
     """poses that differ by whole metres and by a yaw of 0.2 rad: a point posed with its neighbour's matrix is off by metres"""

@@ -281,6 +281,99 @@ def test_trajectory_in_the_reference_limits_and_a_long_polyline(backend):
     assert np.array_equal(got.cpu().numpy(), want) and (want != 255).any()
 
 
+# ---- narrow bands: rows wider than 1024 pixels -------------------------------------------------------------------------------------
+WIDE_H = 9                                                 # no multiple of 7 or of 2: the last band of every width below 4097 is partial
+WIDE = [(1024, 8), (1025, 7), (2731, 2), (4096, 2), (4097, 1), (8192, 1)]
+WIDE_IDS = [f'w{w}' for w, _ in WIDE]
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+@pytest.mark.parametrize('w,band', WIDE, ids=WIDE_IDS)
+def test_wide_rows_colour_and_image(backend, w, band):
+    """clslam_viz_compose's `band = max(1, min(8, 8192 / w))` below 8, down to one pixel row, and viz_compose_kernel's
+    `ylo = blockIdx.x * band`, `yhi = min(h, ylo + band)`: a colour row and an HWC float32 image row in one call, into the middle
+    of a taller destination with wider rows; the bytes around the rectangle stay as they were.  Measured: at most 0.02 s a case
+    on the CPU emulator, under 0.005 s on the MI355X."""
+    from clslam_hip import ops
+    device = use_backend(backend)
+    assert max(1, min(8, 8192 // w)) == band and (band == 1 or WIDE_H % band)
+    rng = np.random.default_rng(w)
+    n, h = 2, WIDE_H
+    depth = (rng.random((n, h, w)) * 30).astype(np.float32)
+    depth[:, ::4, ::97] = np.nan
+    image = rng.random((n, h, w, 3)).astype(np.float32)
+    rr = np.array([[2.0, 20.0], [5.0, 25.0]], np.float32)
+    before = rng.integers(0, 256, (n, 5 + 2 * h + 3, w + 8, 3), dtype=np.uint8)
+    dst = torch.from_numpy(before.copy()).to(device)
+    view = dst[:, :, 4:, :]                      # stride(1) = 3 (w + 8) > 3 w
+    out = ops.viz_compose([ops.viz_cmap_row(torch.from_numpy(depth).to(device), torch.from_numpy(rr).to(device)),
+                           ops.viz_image_row(torch.from_numpy(image).to(device))], n, h, w, dst=view, row0=5)
+    assert out.data_ptr() == view.data_ptr()
+    want = before.copy()
+    for i in range(n):
+        want[i, 5:5 + h, 4:4 + w] = ref.colorize(depth[i], rr[i, 0], rr[i, 1], 'magma_r')
+        want[i, 5 + h:5 + 2 * h, 4:4 + w] = ref.image_row(image[i])
+    assert np.array_equal(dst.cpu().numpy(), want)
+
+
+def _wide_lines(w):
+    """(gt, pred) in a window of one unit per pixel, xlim = (0, w), ylim = (0, 9).  gt: a shallow x-major segment across the full
+    width (w candidate k in every band: the bisection, also where a band is one pixel row), then, after a NaN vertex, a steep
+    y-major one through every band.  pred: a polyline that crosses both, enters from beyond the left border and leaves beyond the
+    right one."""
+    nan = np.nan
+    gt = [[0.5, 1.5], [w - 0.5, 7.5], [nan, nan], [w // 3 + 0.5, 0.5], [w // 3 + 3.5, 8.5]]
+    pred = [[-100.5, 8.2], [w // 2 + 0.5, 0.7], [w // 2 + 2.5, 8.5], [w + 100.5, 1.2], [0.5, 7.5], [w - 0.5, 1.5]]
+    return np.asarray(gt, np.float64), np.asarray(pred, np.float64)
+
+
+def test_the_reference_clipping_is_the_brute_force_rule_on_a_wide_row():
+    """the premise of test_wide_rows_trajectory: on a 9 x 1025 row, where every k of every segment can still be walked, the
+    reference's clipping gives the pixels of the brute-force rule, for the very lines those cases draw"""
+    gt, pred = _wide_lines(1025)
+    lims = dict(xlim=(0.0, 1025.0), ylim=(0.0, float(WIDE_H)))
+    a = ref.trajectory_row(gt, pred, (WIDE_H, 1025), **lims)
+    assert np.array_equal(a, ref.trajectory_row(gt, pred, (WIDE_H, 1025), brute=True, **lims)) and (a != 255).any()
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+@pytest.mark.parametrize('w,band', WIDE, ids=WIDE_IDS)
+def test_wide_rows_trajectory(backend, w, band):
+    """vz_draw_segment's clip against a band of `band < 8` pixel rows (`ylo`, `yhi` from viz_compose_kernel), with `khi - klo >=
+    kVzShortSegment` (the bisection) in a band of one row at w > 4096.  Measured: at most 0.13 s a case on the CPU emulator
+    (most of it the reference's Python loop), 0.03 s on the MI355X."""
+    from clslam_hip import ops
+    device = use_backend(backend)
+    assert max(1, min(8, 8192 // w)) == band
+    h = WIDE_H
+    gt, pred = _wide_lines(w)
+    lims = dict(xlim=(0.0, float(w)), ylim=(0.0, float(h)))
+    want = ref.trajectory_row(gt, pred, (h, w), **lims)
+    shallow = ref.polyline_pixels(gt[:2], h, w, **lims)
+    steep = ref.polyline_pixels(gt[3:], h, w, **lims)
+    assert len(shallow) == w and len({v for _, v in shallow}) == 7 and len(steep) == h == len({v for _, v in steep})
+    both = ref.polyline_pixels(gt, h, w, **lims) & ref.polyline_pixels(pred, h, w, **lims)
+    assert both and (want == np.array(ref.GT_COLOUR, np.uint8)).all(-1).any(axis=1).all()        # gt shows in every pixel row
+    row = ops.viz_traj_row(torch.from_numpy(gt).to(device), torch.from_numpy(pred).to(device), **lims)
+    got = ops.viz_compose([row], 1, h, w)[0]
+    got = got.cpu().numpy()
+    assert np.array_equal(got, want)
+    assert all(tuple(got[v, u]) == ref.PRED_COLOUR for u, v in both)
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+def test_compose_refuses_a_row_wider_than_8192(backend):
+    """the width at which `8192 / w` would be 0 is refused, by the binding, which checks first, with '1 <= w <= 8192'"""
+    from clslam_hip import ops
+    from clslam_hip._lib import ClslamError
+    device = use_backend(backend)
+    plane = torch.zeros((1, 1, 8193), device=device)
+    rng = torch.zeros((1, 2), device=device)
+    with pytest.raises(ClslamError, match='1 <= w <= 8192'):
+        ops.viz_compose([ops.viz_cmap_row(plane, rng)], 1, 1, 8193)
+    assert ops.viz_compose([ops.viz_cmap_row(torch.zeros((1, 1, 8192), device=device), rng)], 1, 1, 8192).shape == (1, 1, 8192, 3)
+
+
 @pytest.mark.parametrize('backend', BACKENDS)
 def test_compose_refuses_bad_arguments(backend):
     from clslam_hip import ops

@@ -216,6 +216,257 @@ def test_determinism(backend):
     assert np.array_equal(_bits(c[0][c[1] == 1]), _bits(a[0][a[1] == 1]))
 
 
+# ---- the sizes at which the scans go multi-level --------------------------------------------------------------------------------
+# Exact clouds (voxel_reference.lattice_cloud): rows and counts are compared bitwise with voxel_exact, the keys of the rows of
+# one-member cells with the reference's.  Every condition a case is there for is asserted on the reference before the kernel runs.
+#
+# Measured, seconds per case, CPU emulator | MI355X (the whole test: cloud, reference, conditions, kernel, comparison):
+#   test_scan_levels        65,536: 1.4 | 0.32     65,537: 0.3 | 0.03     262,147: 0.8 | 0.13     1,048,577: (4.5) | 0.56
+#   test_scan_levels_dropped_rows 0.3 | 0.04    test_scan_levels_min_points 0.6 | 0.05 each    test_scan_levels_fused_poses 0.6 | 0.04
+#   test_determinism_multi_level  1.2 | 0.11       test_scan_sums_two_per_thread  (30) | 6.4, nearly all of it on the host
+# (65,536 also runs the fsum reference on a prefix.)  The slowest emulator case of this file before these took 0.4 s
+# (test_determinism); 262,147 points take twice that, so no row was moved: every row is on the backends the table of sizes names.
+# The figures in brackets are runs outside the suite: 1,048,577 and 16,777,217 points are device-only.
+LEVEL_CASES = [pytest.param(m, b, id=f'{m}-{b}', marks=[pytest.mark.gpu] if b == 'hip' else [])
+               for m, bs in ((65536, ('emu', 'hip')), (65537, ('emu', 'hip')), (262147, ('emu', 'hip')), (1048577, ('hip',)))
+               for b in bs]
+
+
+@functools.lru_cache(maxsize=None)
+def _lattice(m, **kw):
+    """x in [-2, 8), y and z in [-8, 8): every axis straddles the bias, so every key bit below 63 varies.  x is off centre for
+    pass 5 (bit 20 of ix + 2^20, then iy's lowest three): it finds the keys ordered by ix's low 20 bits, the cells from 0 on in
+    front of those below 0, and digit 15 needs ix >= 0 -- with a fifth of the rows below 0 the others reach tile 49 of 65."""
+    pts = V.lattice_cloud(m, seed=m, **{'lo': (-128, -512, -512), **kw})
+    pts.setflags(write=False)
+    return pts
+
+
+def _scan_conditions(pts, vs):
+    """-> the number of radix passes that run.  Asserted for each of them, on the keys in the order that pass finds them (the
+    scatter reads gbase = hist[g] + sums[g / 1024] with g = digit * tiles + tile): where the histogram fills more than one scan
+    block, digit 15 occurs in a tile with 15 * tiles + tile >= 1024 and the sums entry it reads is not zero -- a second level
+    that returned zeros, or sums[0], would misplace those keys.  Two passes cannot hold digit 15 in any cloud within 2^19 cells of
+    the origin: pass 15 (bits 60-63: bit 63 is clear in every cell key) and pass 10 (bits 40-43 start with bits 19 and 20 of
+    iy + 2^20, which are 01 below the bias and 10 from it on).  There the same is asserted of the largest digit that occurs
+    instead, if its entries lie beyond the first scan block at all."""
+    m = len(pts)
+    tiles = -(-m // T)
+    n_sums = -(-16 * tiles // T)
+    trace = V.radix_trace(pts, vs)
+    tile = np.arange(m) // T
+    for p, d in trace:
+        if n_sums == 1:
+            continue
+        g = d.astype(np.int64) * tiles + tile
+        top = 15 if p not in (10, 15) else int(d.max())
+        late = (d == top) & (g >= T)
+        if top == 15 or top * tiles + tiles - 1 >= T:
+            assert late.any(), (p, top)
+            assert g.min() < (g[late] // T).min() * T, p                                   # keys in front of that scan block
+    return len(trace)
+
+
+def _check_exact(backend, case, out, ref, vs, passes):
+    rows, counts, info = out
+    print(f'[voxel {backend}] {case}: {len(ref["counts"])} cells, largest {int(ref["counts"].max())}, single '
+          f'{int((ref["counts"] == 1).sum())}, dropped {ref["dropped"]}, passes {passes}; kernel: {info}')
+    assert info['cells'] == len(ref['counts']) == len(counts), case
+    assert info['dropped'] == ref['dropped'] and info['passes'] == passes, case
+    assert np.array_equal(counts, ref['counts']), case
+    assert np.array_equal(_bits(rows), _bits(ref['rows'])), case
+    one = ref['counts'] == 1
+    assert np.array_equal(V.row_keys(rows[one], vs), ref['keys'][one]), case                # exact rows lie in their cells
+
+
+def _every_cell(ref):
+    return {'counts': ref['all_counts']}
+
+
+@pytest.mark.parametrize('m,backend', LEVEL_CASES)
+def test_scan_levels(m, backend):
+    """pcl_voxel_scatter_kernel's `gbase[t] = hist[g] + sums[g / kVxTile]`, pcl_voxel_scan_kernel as more than one block and
+    pcl_voxel_scan_sums_kernel over more than one value; at 1,048,577 also pcl_voxel_heads_kernel's `sums[blockIdx.x / kVxTile]`.
+      65,536     n_hist == 1024: one scan block, exactly full; every tile full (the 16-byte loads in every tile)
+      65,537     n_sums == 2; the last tile holds one key; the second scan block holds 16 live entries
+      262,147    n_sums == 5, 257 tiles, a partial last tile
+      1,048,577  1025 tiles: head_sums == 2, the heads kernel reads sums[1]; n_sums == 17.  Only tile 1024 reads sums[1], and it
+                 holds one key, the largest: that cell is given exactly one member, so position 1024 * 1024 is a run head and
+                 the heads before it make sums[1] non-zero (both asserted on the reference)
+    The cloud is _lattice's: x in [-2, 8) (off centre for pass 5, see there), y and z in [-8, 8), so the cell indices straddle
+    the 2^20 bias on every axis, every key bit below 63 varies and all 16 passes run.  Times: the table above LEVEL_CASES."""
+    dev = use_backend(backend)
+    vs = 0.25
+    pts = _lattice(m, top=(1, vs)) if m > T * T else _lattice(m)
+    tiles = -(-m // T)
+    n_sums, head_sums = -(-16 * tiles // T), -(-tiles // T)
+    assert (n_sums, head_sums, m % T) == {65536: (1, 1, 0), 65537: (2, 1, 1), 262147: (5, 1, 3), 1048577: (17, 2, 1)}[m]
+    ref = V.voxel_exact(pts, vs)
+    _has_work(ref)
+    passes = _scan_conditions(pts, vs)
+    assert passes == 16 == _passes(ref['keys'])
+    if head_sums > 1:                                # a head whose block reads sums[1], and heads in front of it
+        start = np.cumsum(ref['all_counts']) - ref['all_counts']
+        assert (start >= T * T).any() and (start < T * T).any() and start[-1] == m - 1
+    if m == 65536:                                   # voxel_exact against the fsum reference, where that one is affordable
+        few, slow = V.voxel_exact(pts[:4096], vs), V.voxel(pts[:4096], vs)
+        _has_work(few)
+        assert np.array_equal(few['keys'], slow['keys']) and np.array_equal(few['counts'], slow['counts'])
+        assert np.array_equal(_bits(few['rows']), _bits(slow['mean'].astype(np.float32)))
+        other = V.voxel_exact(pts, vs, method='bincount')                                # and its two forms against each other
+        assert all(np.array_equal(ref[k], other[k]) for k in ('keys', 'counts', 'all_counts'))
+        assert np.array_equal(_bits(ref['rows']), _bits(other['rows']))
+    _check_exact(backend, f'M = {m}', _run(dev, pts, vs), ref, vs, passes)
+
+
+def _dropped_cloud(m):
+    """z below 0 only: without the dropped rows the last pass would not run.  About 1 % of the rows get a NaN or an infinity in
+    one of their six values, among them the last two rows: the last tile of the input is nothing but a dropped row."""
+    rng = np.random.default_rng(77)
+    clean = _lattice(m, hi=(512, 512, 0))
+    pts = clean.copy()
+    hit = np.unique(np.concatenate([rng.choice(m, m // 100, replace=False), [0, T - 1, T, m - 2, m - 1]]))
+    pts[hit, rng.integers(0, 6, len(hit))] = rng.choice(np.array([np.nan, np.inf, -np.inf], np.float32), len(hit))
+    return clean, pts, len(hit)
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+def test_scan_levels_dropped_rows(backend):
+    """65,537 points (n_sums == 2: the scatter's `sums[g / kVxTile]`) of which 1 % are dropped: `dropped` is not zero, the last
+    pass runs only to move them (digit 8 against the cells' one digit), and mv < M in pcl_voxel_heads_kernel and
+    pcl_voxel_reduce_kernel.  Times: the table above LEVEL_CASES."""
+    dev = use_backend(backend)
+    m, vs = 65537, 0.25
+    clean, pts, n_hit = _dropped_cloud(m)
+    ref = V.voxel_exact(pts, vs)
+    _has_work(ref)
+    assert ref['dropped'] == n_hit >= m // 100 and ref['all_counts'].sum() == m - n_hit
+    assert not np.isfinite(pts[m - 1]).all() and not np.isfinite(pts[0]).all()
+    assert 15 not in [p for p, _ in V.radix_trace(clean, vs)] and V.radix_trace(pts, vs)[-1][0] == 15
+    passes = _scan_conditions(pts, vs)
+    assert passes == _passes(ref['keys']) + 1 == 13
+    out = _run(dev, pts, vs)
+    assert np.isfinite(out[0]).all()
+    _check_exact(backend, 'dropped rows', out, ref, vs, passes)
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+@pytest.mark.parametrize('min_points', [2, 3])
+def test_scan_levels_min_points(backend, min_points):
+    """vx_head's `K[i + min_points - 1]` across tile and scan-block boundaries, at 65,537 points (n_sums == 2).  The cell of the
+    largest key holds exactly min_points members, so its run starts before position 65,536 = 64 * 1024 and ends on it: the head
+    in the last full tile reads the one key of the last tile.  Times: the table above LEVEL_CASES."""
+    dev = use_backend(backend)
+    m, vs = 65537, 0.5
+    pts = _lattice(m, top=(min_points, vs))
+    every, ref = V.voxel_exact(pts, vs), V.voxel_exact(pts, vs, min_points)
+    _has_work(_every_cell(ref))                      # of every cell: no cell of one member survives min_points >= 2
+    assert 0 < len(ref['counts']) < len(every['counts']) and ref['counts'].min() == min_points
+    start = np.cumsum(every['all_counts']) - every['all_counts']
+    last = start + every['all_counts'] - 1
+    straddles = [(int(a), int(b)) for a, b, n in zip(start, last, every['all_counts'])
+                 if n >= min_points and any(a < T * k <= b for k in range(64, m // T + 1))]
+    assert (m - min_points, m - 1) in straddles, straddles
+    assert sum(1 for a, b in zip(start, last) if a // T != b // T) > 10                       # and runs across tile boundaries
+    passes = _scan_conditions(pts, vs)
+    assert passes == 16
+    out = _run(dev, pts, vs, min_points=min_points)
+    _check_exact(backend, f'min_points {min_points}', out, ref, vs, passes)
+    all_rows, all_counts, _ = _run(dev, pts, vs)
+    assert np.array_equal(_bits(out[0]), _bits(all_rows[all_counts >= min_points]))               # the same rows, fewer of them
+
+
+def _signed_permutations():
+    """five poses that keep a lattice cloud on the lattice, exactly: an axis permutation with sign flips, and a translation in
+    64ths that is zero on no axis (so no coordinate comes out as -0.0)"""
+    perms = [((0, 1, 2), (1, -1, 1)), ((1, 2, 0), (-1, 1, 1)), ((0, 2, 1), (1, -1, 1)), ((2, 0, 1), (-1, -1, 1)),
+             ((1, 0, 2), (-1, -1, -1))]
+    shifts = [(37, -101, 5), (-64, 3, 200), (1, 1, -1), (255, -256, 77), (-130, 64, -9)]  # the third keeps x where _lattice put it
+    out = []
+    for (perm, sign), shift in zip(perms, shifts):
+        P = np.eye(4)
+        P[:3, :3] = 0
+        for r in range(3):
+            P[r, perm[r]] = sign[r]
+        P[:3, 3] = np.asarray(shift) / 64.0
+        out.append(P)
+    return np.stack(out)
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+def test_scan_levels_fused_poses(backend):
+    """65,537 points (n_sums == 2: the scatter's `sums[g / kVxTile]`) in five segments with boundaries at 0, 1, 65,536 and 65,537:
+    an empty first segment, one point, 65,535 points, an empty segment whose pose is NaN, and the one point of the last tile.  The
+    poses are signed axis permutations with translations in 64ths: pose_apply is exact, the posed cloud stays on the lattice, and
+    the fused result equals the reference on the posed points and the filter of the transformed cloud, bitwise.  Times: the
+    table above LEVEL_CASES."""
+    dev = use_backend(backend)
+    m, vs = 65537, 0.25
+    pts = _lattice(m)
+    offsets = np.array([0, 0, 1, 65536, 65536, 65537], np.int64)
+    poses = _signed_permutations()
+    poses[3] = np.nan
+    posed = pts.copy()
+    for f in range(5):
+        a, b = offsets[f], offsets[f + 1]
+        if b > a:
+            posed[a:b, :3] = (pts[a:b, :3].astype(np.float64) @ poses[f][:3, :3].T + poses[f][:3, 3]).astype(np.float32)
+    assert V.is_lattice(posed, vs) and not np.signbit(posed[posed == 0]).any()
+    ref = V.voxel_exact(posed, vs)
+    _has_work(ref)
+    passes = _scan_conditions(posed, vs)
+    assert passes == 16
+    world = ops.pcl_transform(_t(pts, dev), offsets, _t(poses, dev))
+    assert np.array_equal(_bits(world.cpu().numpy()), _bits(posed))
+    two = ops.pcl_voxel_downsample(world, vs, return_info=True)
+    _check_exact(backend, 'transformed, then filtered', (two[0].cpu().numpy(), two[1].cpu().numpy(), two[2]), ref, vs, passes)
+    _check_exact(backend, 'fused poses', _run(dev, pts, vs, offsets=offsets, poses=poses), ref, vs, passes)
+
+
+@pytest.mark.parametrize('backend', BACKENDS)
+def test_determinism_multi_level(backend):
+    """two runs of the 262,147-point case (n_sums == 5: the scatter's `sums[g / kVxTile]` in 257 blocks that run in any order) are
+    bit-equal, and equal to the reference.  Times: the table above LEVEL_CASES."""
+    dev = use_backend(backend)
+    m, vs = 262147, 0.25
+    pts = _lattice(m)
+    ref = V.voxel_exact(pts, vs)
+    _has_work(ref)
+    passes = _scan_conditions(pts, vs)
+    a = _run(dev, pts, vs)
+    b = _run(dev, pts, vs)
+    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+    _check_exact(backend, 'second run', b, ref, vs, passes)
+
+
+@pytest.mark.gpu
+def test_scan_sums_two_per_thread():
+    """pcl_voxel_scan_sums_kernel's `per = ceil(n / 256)` at per == 2: 16,777,217 points are 16,385 tiles and n_sums == 257, so
+    thread t scans sums 2 t and 2 t + 1, thread 128 takes the one that is left and the `lo` / `hi` clamp leaves the threads from
+    129 on empty.  (The heads' second level has 17 sums here.)  0.4 GB of cloud and as much scratch on the device; on the host the
+    process peaks at 2.2 GB (the cloud, and the float64 cell indices the reference forms from it).  The cloud straddles the bias
+    in x only: x in [-8, 8), y in [0, 2), z in [-0.5, 0) for all but some 4,000 rows with z in [-8, 0), which are mostly alone in
+    their cells -- the keys vary in the digits 0-5, 10 and 11, eight passes.  Host time is the cost (the table above LEVEL_CASES):
+    the cloud is one integers() call per array and the reference np.bincount over the 64 x 8 x 32 cells of the box."""
+    dev = use_backend('hip')
+    m, vs = (1 << 24) + 1, 0.25
+    tiles = -(-m // T)
+    assert -(-16 * tiles // T) == 257 and -(-257 // 256) == 2 and min(129 * 2, 257) == 257
+    lo = np.empty((m, 3), np.int16)                  # per row for z only; int16 bounds, 0.1 GB
+    lo[:] = (-512, 0, -32)
+    lo[np.random.default_rng(3).choice(m, 4000, replace=False), 2] = -512
+    pts = V.lattice_cloud(m, seed=m, lo=lo, hi=(512, 128, 0))
+    del lo
+    ref = V.voxel_exact(pts, vs)
+    _has_work(ref)
+    passes = _scan_conditions(pts, vs)
+    assert passes == 8 == _passes(ref['keys'])
+    try:
+        _check_exact('hip', f'M = {m}', _run(dev, pts, vs), ref, vs, passes)
+    finally:
+        torch.cuda.empty_cache()
+
+
 # ---- fused poses --------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _frames():
