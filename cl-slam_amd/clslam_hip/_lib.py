@@ -134,6 +134,18 @@ _SIGNATURES = {
     'clslam_disp_mean_chunks': [],
     'clslam_disp_mean': [fptr, fptr, i32, i32, C.c_void_p],
     'clslam_loss_finalize': [C.POINTER(LossDesc), C.c_void_p],
+    # mask_dynamic=True (additive, ABI 114)
+    'clslam_photo_automask_pyramid_masked': [fptr, fptr, fptr, fptr, C.c_uint64, C.c_uint64, fptr, fptr, fptr, fptr, fptr, i32, i32,
+                                             i32, C.c_void_p],
+    'clslam_smooth_locate': [C.POINTER(fptr), fptr, i32, i32, i32, C.c_void_p],
+    'clslam_loss_finalize_masked': [C.POINTER(LossDesc), fptr, fptr, fptr, C.c_void_p],
+    'clslam_loss_bwd2_pyramid_masked': [C.POINTER(fptr), fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, i32,
+                                        i32, i32, C.c_float, C.c_float, C.c_void_p],
+    'clslam_smooth_pos_bwd': [C.POINTER(fptr), fptr, fptr, i32, C.POINTER(fptr), i32, i32, i32, C.c_void_p],
+    'clslam_smooth_intended_masked_fwd': [C.POINTER(fptr), C.POINTER(fptr), C.POINTER(fptr), fptr, fptr, i32, i32, i32, C.c_void_p],
+    'clslam_smooth_intended_masked_finalize': [fptr, fptr, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_float, C.c_void_p],
+    'clslam_smooth_intended_masked_bwd': [C.POINTER(fptr), C.POINTER(fptr), C.POINTER(fptr), fptr, fptr, C.POINTER(fptr), i32, i32,
+                                          i32, C.c_float, C.c_void_p],
     'clslam_pair_loss': [fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_float, C.c_float, C.c_void_p],
     'clslam_pair_loss_rng': [fptr, fptr, fptr, fptr, fptr, C.c_uint64, C.c_uint64, fptr, fptr, fptr, fptr, i32, i32, i32, C.c_float,
                              C.c_float, C.c_void_p],

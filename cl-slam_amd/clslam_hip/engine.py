@@ -115,7 +115,7 @@ def _device_streams(device) -> Dict[str, Any]:
 class Engine:
     def __init__(self, height: int, width: int, device: torch.device, *, min_depth: Optional[float],
                  max_depth: Optional[float], disparity_smoothness: float, velocity_loss_scaling: Optional[float],
-                 reference_quirks: bool = True) -> None:
+                 reference_quirks: bool = True, mask_dynamic: bool = False) -> None:
         lib = get_lib()  # raises if libclslam_hip.so is missing -- there is no fallback
         if device.type != lib.device_type:
             raise ClslamError(f'engine on {device} but {lib.path.name} executes on {lib.device_type}; the MI355X path '
@@ -125,6 +125,10 @@ class Engine:
         # reference_quirks=False: the per-sample edge-aware smoothness the reference evidently meant instead of
         # the flattened-batch behaviour of dpp.py:1148-1176; opt-in, parity runs use the default
         self.smooth_intended = not reference_quirks
+        # mask_dynamic=True (dpp.py:1063-1090): "potentially dynamic" pixels (inputs['mask', 0, s] == 1) leave the reprojection
+        # mean and the smoothness; the reprojection term becomes one mean over the static pixels of the whole minibatch
+        # (no sample weights).  A second loss stage beside the unmasked one (_masked_loss / _masked_loss_backward).
+        self.mask_dynamic = bool(mask_dynamic)
         if min_depth is None and max_depth is not None:
             raise ValueError('min_depth is None')        # disp_to_depth, utils.py:134-135
         self.H, self.W, self.device = height, width, device
@@ -705,6 +709,11 @@ class Engine:
         for k in (('camera_matrix', 0), ('inv_camera_matrix', 0)):
             if tuple(inputs[k].shape) != (B, 4, 4):
                 raise ClslamError(f'{k} must be ({B}, 4, 4), got {tuple(inputs[k].shape)}')
+        if self.mask_dynamic:
+            for s in range(4):
+                t = inputs['mask', 0, s]          # a missing mask is a KeyError naming the key, like dpp.py:1066 / 1081
+                if t.numel() != B * (H >> s) * (W >> s):
+                    raise ClslamError(f"('mask', 0, {s}) must be ({B}, 1, {H >> s}, {W >> s}), got {tuple(t.shape)}")
 
     def _fresh_output_planes(self, ws, B: int) -> None:
         """The reference returns fresh tensors from every call: the output planes are (cheap, cached) new allocations that
@@ -818,6 +827,9 @@ class Engine:
             self._main.wait_event(c.id_ready)
         else:
             c.have_noise = self._identity_and_noise(ws, c)
+        if self.mask_dynamic:
+            self._masked_loss(ws, c, sample_w, smooth_w, K, Kinv)
+            return
         # all four scales in one launch; reprojection maps stay in registers, only the selected frame's
         # SSIM coefficients are kept for the backward
         if c.have_noise:
@@ -852,6 +864,49 @@ class Engine:
             ops.smooth_intended_finalize(ws.si_partial, ws.means, sample_w, ws.losses, ws.si_aux, B, H, W, self.smooth_scale)
         ws.ctx = SimpleNamespace(rgb=rgb, K=K, Kinv=Kinv, d0=d0, d1=d1, sample_w=sample_w, n_smooth=n_smooth,
                                  aux=aux if n_smooth else None, B=B, rgb0=rgb0)
+
+    def _masked_loss(self, ws, c, sample_w: torch.Tensor, smooth_w: Optional[torch.Tensor], K, Kinv) -> None:
+        """The rest of _loss_stage under mask_dynamic (dpp.py:1063-1090): masked photometric sums and static counts, the
+        positions of the quirk's smoothness terms on the masked planes (or the masked per-sample smoothness), the finalize.
+        Nothing is read back: N_static stays on the device (ws.mstat) for the backward."""
+        inputs, rgb, B, H, W = c.inputs, c.rgb, c.B, self.H, self.W
+        masks = [self._img(inputs['mask', 0, s]).reshape(B, H >> s, W >> s) for s in range(4)]
+        if getattr(ws, 'mstat', None) is None:
+            ws.cnt_partial = torch.zeros(B, ws.nblk, dtype=torch.int32, device=self.device)
+            ws.loc = torch.full((4, 2, 2 * B), -1, dtype=torch.int32, device=self.device)
+            ws.mstat = torch.zeros(2, device=self.device)
+            ws.smooth_aux_m = torch.zeros(4, 2 + 2 * B, device=self.device)
+        if c.have_noise:
+            seed = offset = 0
+        else:
+            seed, offset = self._next_noise_draw()
+        ops.photo_automask_pyramid_masked(ws.warped, rgb[0], ws.idmap, ws.noise if c.have_noise else None, seed, offset, masks[0],
+                                          ws.sel, ws.coef if c.train else None, ws.partial, ws.cnt_partial, B, H, W)
+        ops.disp_mean_pyramid(ws.disp, ws.means, H, W)
+        n_smooth = 0 if (smooth_w is None or self.smooth_intended) else int(smooth_w.numel())
+        if n_smooth and n_smooth != B:
+            raise ClslamError(f'mask_dynamic: the masked smoothness has one term per sample, got {n_smooth} weights for {B} samples')
+        if n_smooth:
+            ops.smooth_locate(masks, ws.loc, H, W)
+        d0 = inputs['relative_distance', 0].to(torch.float64).reshape(-1).contiguous() if self.vel_scale > 0 else None
+        d1 = inputs['relative_distance', 1].to(torch.float64).reshape(-1).contiguous() if self.vel_scale > 0 else None
+        rgb0 = [self._img(inputs['rgb', 0, s]) for s in range(4)]
+        aux = ws.smooth_aux_m if n_smooth else None
+        ops.loss_finalize_masked([ws.partial[s] for s in range(4)], ws.disp, rgb0, [ws.means[s] for s in range(4)], ws.pose, d0, d1,
+                                 sample_w, smooth_w if n_smooth else None, ws.losses, aux, ws.cnt_partial,
+                                 ws.loc if n_smooth else None, ws.mstat, B, ws.nblk, H, W, n_smooth, self.smooth_scale,
+                                 self.vel_scale)
+        if self.smooth_intended:
+            if getattr(ws, 'sim_partial', None) is None:
+                chunks = ops.smooth_intended_chunks()
+                ws.sim_partial = torch.empty(4, B, chunks, 2, device=self.device)
+                ws.sim_cnt = torch.zeros(4, B, chunks, 2, dtype=torch.int32, device=self.device)
+                ws.sim_aux = torch.empty(4, B, 4, device=self.device)
+            ops.smooth_intended_masked_fwd(ws.disp, rgb0, masks, ws.sim_partial, ws.sim_cnt, H, W)
+            ops.smooth_intended_masked_finalize(ws.sim_partial, ws.sim_cnt, ws.means, sample_w, ws.losses, ws.sim_aux, B, H, W,
+                                                self.smooth_scale)
+        ws.ctx = SimpleNamespace(rgb=rgb, K=K, Kinv=Kinv, d0=d0, d1=d1, sample_w=sample_w, n_smooth=n_smooth, aux=aux, B=B,
+                                 rgb0=rgb0, masks=masks)
 
     def _memo_lookup(self, x: torch.Tensor) -> Optional[List[torch.Tensor]]:
         """Features of the last run_encoder('depth_encoder', ...) call if `x` (1,3,H,W on the device, already complete on the
@@ -1044,11 +1099,22 @@ class Engine:
     def _loss_backward(self, ws, t, c) -> None:
         """loss -> disparity logits (t.dz_disp) and pose-decoder output (t.dpose); records `inputs_released` behind them."""
         H, W = self.H, self.W
-        ops.loss_bwd2_pyramid(ws.disp, ws.sel, ws.coef, ws.warped, c.rgb[0], c.rgb[-1], c.rgb[1], c.Kinv, ws.P, c.sample_w,
-                              t.ddisp_up, t.dp_partial, self.min_depth, self.max_depth)
-        ops.disp_grad_pyramid(t.ddisp_up, ws.disp, c.aux if c.n_smooth else None, c.n_smooth, t.dz_disp, H, W)
-        if self.smooth_intended:
-            ops.smooth_intended_bwd(ws.disp, c.rgb0, ws.si_aux, c.sample_w, t.dz_disp, H, W, self.smooth_scale)
+        if self.mask_dynamic:
+            # a static pixel carries 1 / (4 N_static) (ws.mstat, device-resident), a dynamic one 0; the smoothness terms sit at
+            # the located positions, so the row-0 layout of disp_grad_pyramid does not apply: their gradient is added behind it
+            ops.loss_bwd2_pyramid_masked(ws.disp, ws.sel, ws.coef, ws.warped, c.rgb[0], c.rgb[-1], c.rgb[1], c.Kinv, ws.P,
+                                         c.masks[0], ws.mstat, t.ddisp_up, t.dp_partial, self.min_depth, self.max_depth)
+            ops.disp_grad_pyramid(t.ddisp_up, ws.disp, None, 0, t.dz_disp, H, W)
+            if c.n_smooth:
+                ops.smooth_pos_bwd(ws.disp, c.aux, ws.loc, c.n_smooth, t.dz_disp, H, W)
+            if self.smooth_intended:
+                ops.smooth_intended_masked_bwd(ws.disp, c.rgb0, c.masks, ws.sim_aux, c.sample_w, t.dz_disp, H, W, self.smooth_scale)
+        else:
+            ops.loss_bwd2_pyramid(ws.disp, ws.sel, ws.coef, ws.warped, c.rgb[0], c.rgb[-1], c.rgb[1], c.Kinv, ws.P, c.sample_w,
+                                  t.ddisp_up, t.dp_partial, self.min_depth, self.max_depth)
+            ops.disp_grad_pyramid(t.ddisp_up, ws.disp, c.aux if c.n_smooth else None, c.n_smooth, t.dz_disp, H, W)
+            if self.smooth_intended:
+                ops.smooth_intended_bwd(ws.disp, c.rgb0, ws.si_aux, c.sample_w, t.dz_disp, H, W, self.smooth_scale)
         ops.pose_bwd(t.dp_partial, 4, t.nb2, ws.pose, c.K, c.d0, c.d1, c.sample_w, self.vel_scale, t.dpose)
         self.inputs_released = None
         if self._caller is not None:

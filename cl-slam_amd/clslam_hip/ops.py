@@ -655,6 +655,64 @@ def loss_bwd2_pyramid(disps, sel, coef_sel, warped, target, src_m1, src_p1, inv_
                         _nd(min_depth), _nd(max_depth), _stream(ddisp_up))
 
 
+# ---- mask_dynamic=True: the masked loss (include/clslam_hip.h "mask_dynamic = True") --------------------------------------------
+def photo_automask_pyramid_masked(warped, target, idmap, noise, seed, offset, mask0, sel, coef_sel, partial, cnt_partial,
+                                  batch, H, W):
+    """noise (4,B,2,H,W) or None with seed != 0 (drawn in the kernel); mask0 (B,H,W) fp32; cnt_partial (B,nblk) int32"""
+    if noise is None and not seed:
+        raise _lib.ClslamError('photo_automask_pyramid_masked: a noise tensor or a non-zero seed')
+    _lib.get_lib().call('clslam_photo_automask_pyramid_masked', _p(warped), _p(target), _p(idmap), _p(noise), int(seed), int(offset),
+                        _p(mask0), _pa(sel, torch.uint8), _p(coef_sel), _p(partial), _pa(cnt_partial, torch.int32), batch, H, W,
+                        _stream(warped))
+
+
+def smooth_locate(masks, loc, H, W):
+    """masks: four (B,h_s,w_s) fp32 planes; loc (4,2,2B) int32"""
+    _lib.get_lib().call('clslam_smooth_locate', _ptr4(masks), _pa(loc, torch.int32), masks[0].shape[0], H, W, _stream(loc))
+
+
+def loss_finalize_masked(partials, disps, rgb0s, means, pose, dist0, dist1, sample_w, smooth_w, losses, smooth_aux, cnt_partial,
+                         loc, mstat, batch, nblk, H, W, n_smooth, smooth_scale, vel_scale):
+    d = _lib.LossDesc()
+    for s in range(4):
+        d.partial[s] = _p(partials[s]); d.disp[s] = _p(disps[s]); d.rgb0[s] = _p(rgb0s[s]); d.means[s] = _p(means[s])
+    d.pose = _p(pose)
+    d.dist0 = _pa(dist0, torch.float64); d.dist1 = _pa(dist1, torch.float64)
+    d.sample_w = _p(sample_w); d.smooth_w = _p(smooth_w); d.losses = _p(losses); d.smooth_aux = _p(smooth_aux)
+    d.batch, d.nblk, d.H, d.W, d.n_smooth = batch, nblk, H, W, n_smooth
+    d.smooth_scale, d.vel_scale = float(smooth_scale), float(vel_scale or 0.0)
+    _lib.get_lib().call('clslam_loss_finalize_masked', C.byref(d), _pa(cnt_partial, torch.int32), _pa(loc, torch.int32), _p(mstat),
+                        _stream(losses))
+
+
+def loss_bwd2_pyramid_masked(disps, sel, coef_sel, warped, target, src_m1, src_p1, inv_k, proj, mask0, inv_n, ddisp_up, dp_partial,
+                             min_depth, max_depth):
+    B, H, W = ddisp_up.shape[1], ddisp_up.shape[-2], ddisp_up.shape[-1]
+    _lib.get_lib().call('clslam_loss_bwd2_pyramid_masked', _ptr4(disps), _pa(sel, torch.uint8), _p(coef_sel), _p(warped), _p(target),
+                        _p(src_m1), _p(src_p1), _p(inv_k), _p(proj), _p(mask0), _p(inv_n), _p(ddisp_up),
+                        _pa(dp_partial, torch.float64), B, H, W, _nd(min_depth), _nd(max_depth), _stream(ddisp_up))
+
+
+def smooth_pos_bwd(disps, smooth_aux, loc, n_smooth, dzs, H, W):
+    _lib.get_lib().call('clslam_smooth_pos_bwd', _ptr4(disps), _p(smooth_aux), _pa(loc, torch.int32), n_smooth, _ptr4(dzs),
+                        disps[0].shape[0], H, W, _stream(smooth_aux))
+
+
+def smooth_intended_masked_fwd(disps, rgb0, masks, partial, cnt, H, W):
+    _lib.get_lib().call('clslam_smooth_intended_masked_fwd', _ptr4(disps), _ptr4(rgb0), _ptr4(masks), _p(partial),
+                        _pa(cnt, torch.int32), disps[0].shape[0], H, W, _stream(partial))
+
+
+def smooth_intended_masked_finalize(partial, cnt, means, sample_w, losses, aux, batch, H, W, smooth_scale):
+    _lib.get_lib().call('clslam_smooth_intended_masked_finalize', _p(partial), _pa(cnt, torch.int32), _p(means), _p(sample_w),
+                        _p(losses), _p(aux), batch, H, W, float(smooth_scale), _stream(losses))
+
+
+def smooth_intended_masked_bwd(disps, rgb0, masks, aux, sample_w, dz, H, W, smooth_scale):
+    _lib.get_lib().call('clslam_smooth_intended_masked_bwd', _ptr4(disps), _ptr4(rgb0), _ptr4(masks), _p(aux), _p(sample_w),
+                        _ptr4(dz), disps[0].shape[0], H, W, float(smooth_scale), _stream(aux))
+
+
 # ---- SE(3) pose-graph optimisation (csrc/pose_graph.hip; the Levenberg control is clslam_hip/pose_graph.py) ----------------
 def _pd(t):
     return _pa(t, torch.float64)

@@ -149,3 +149,25 @@ def make_noise(B: int, H: int, W: int, seed: int, num_scales: int = 4) -> Dict[i
         z = (u.sum(0) - 2.0) * math.sqrt(3.0)
         out[s] = torch.from_numpy((z * 1e-5).astype(np.float32))
     return out
+
+
+def make_masks(B: int, H: int, W: int, seed: int, dynamic: float = 0.3, num_scales: int = 4, rect=None,
+               static_values=(0.0,)) -> Dict[Any, torch.Tensor]:
+    """inputs['mask', 0, s] for s < num_scales as the datasets build them with with_mask=True: float32 (B,1,H>>s,W>>s), 1 = a
+    "potentially dynamic" pixel, and every scale a plane of its own (drawn independently here: nothing is derived from
+    scale 0).  `dynamic`: the fraction of pixels set to exactly 1; the others cycle through `static_values` (anything but 1
+    is static under dpp.py:1066-1067, e.g. (0.0, 0.5, 2.0)).  rect = (b, y0, y1, x0, x1) in scale-0 pixels additionally marks
+    that rectangle of sample b dynamic at every scale (the rows / columns it touches at the coarser ones)."""
+    out: Dict[Any, torch.Tensor] = {}
+    for s in range(num_scales):
+        h, w = H >> s, W >> s
+        u = hash_uniform(2 * B * h * w, seed * 100 + 50 + s).reshape(2, B, 1, h, w)
+        vals = np.asarray(static_values, dtype=np.float32)
+        m = vals[np.minimum((u[1] * len(vals)).astype(np.int64), len(vals) - 1)]
+        m = np.where(u[0] < dynamic, np.float32(1.0), m).astype(np.float32)
+        if rect is not None:
+            b, y0, y1, x0, x1 = rect
+            f = 1 << s
+            m[b, 0, y0 // f:-(-y1 // f), x0 // f:-(-x1 // f)] = 1.0
+        out['mask', 0, s] = torch.from_numpy(m)
+    return out

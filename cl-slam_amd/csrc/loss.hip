@@ -16,6 +16,25 @@ namespace clslam {
 
 __device__ __forceinline__ int refl(int i, int n) { return reflect_idx(i, n); }
 
+// Ballot of the masked kernels below: bit l = predicate of lane l, the same 64-bit mask in every lane; call from wave-uniform
+// control flow only.  On the GPU one v_cmp (__ballot).  A host build of these sources has the wave primitives of
+// clslam/intrin.h and no ballot: there each lane contributes its own bit and six xor-shuffle steps OR them together (the two
+// 32-bit halves travel as float bit patterns, like the 64-bit sums of ingest.hip).
+#if CLSLAM_DEVICE_BUILD
+__device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __ballot(p ? 1 : 0); }
+#else
+inline unsigned long long wave_ballot(bool p) {
+    const int l = (int)(threadIdx.x & 63);
+    unsigned lo = (p && l < 32) ? 1u << l : 0u, hi = (p && l >= 32) ? 1u << (l - 32) : 0u;
+    for (int m = 1; m < 64; m <<= 1) {
+        lo |= __float_as_uint(wave_shfl_xor(__uint_as_float(lo), m));
+        hi |= __float_as_uint(wave_shfl_xor(__uint_as_float(hi), m));
+    }
+    return ((unsigned long long)hi << 32) | lo;
+}
+#endif
+__device__ __forceinline__ int popcount64(unsigned long long m) { return __builtin_popcountll(m); }
+
 // x / 9 correctly rounded in 3 instructions (Markstein: q = RN(x * r), q' = RN(q + RN(x - 9q) * r) with
 // r = RN(1/9)) instead of the ~10 of an IEEE division.  The 3x3 window means feed sigma = E[x^2] - mu^2, a
 // cancellation that amplifies a 1-ulp difference in the means to ~1e-5 in the SSIM value -- enough to flip
@@ -81,12 +100,18 @@ __global__ __launch_bounds__(256) void tie_break_noise_kernel(float* __restrict_
     out[2 * e] = a; out[2 * e + 1] = b;
 }
 
-template <bool TRAIN>
+// MASKED (mask_dynamic, dpp.py:1063-1069): mask0 = ('mask', 0, 0) (B,H,W); a pixel is static iff its value != 1.0f.  Only
+// static pixels enter the block sum; the scale-0 blocks also write how many there are in the tile (cnt_partial [B][nblk], the
+// same for every scale: source_scale = 0).  sel / coef are written for every pixel as without the mask.  The unmasked
+// instantiations compile to what they were: everything the mask adds sits behind `if constexpr (MASKED)`.
+template <bool TRAIN, bool MASKED = false>
 __global__ __launch_bounds__(256) void photo_automask_kernel(const float* __restrict__ warped_all, const float* __restrict__ target,
                                                              const float* __restrict__ idmap, const float* __restrict__ noise_all,
                                                              unsigned char* __restrict__ sel_all, float* __restrict__ coef_sel_all,
                                                              float* __restrict__ partial_all, int B, int H, int W, int tilesX,
-                                                             unsigned long long seed, unsigned long long rng_offset) {
+                                                             unsigned long long seed, unsigned long long rng_offset,
+                                                             const float* __restrict__ mask0 = nullptr,
+                                                             unsigned* __restrict__ cnt_partial = nullptr) {
     // The two source frames of a pixel travel as ONE packed pair (f32x2 = v_pk_* arithmetic, ds_read_b64): the kernel is
     // VALU-bound (~900 issue slots per pixel before, two thirds of them per frame), not LDS- or HBM-bound.
     __shared__ float tl[3][PA_PH * PA_PW];   // target
@@ -120,6 +145,7 @@ __global__ __launch_bounds__(256) void photo_automask_kernel(const float* __rest
     }
     __syncthreads();
     float s = 0.f;
+    [[maybe_unused]] unsigned stat = 0;       // MASKED: bit `it` = the thread's pixel of that pass is inside the image and static
 #pragma unroll 1
     for (int it = 0; it < (PA_TH * PA_TW) / 256; ++it) {
         const int lp = threadIdx.x + it * 256;
@@ -186,11 +212,26 @@ __global__ __launch_bounds__(256) void photo_automask_kernel(const float* __rest
                 for (int q = 0; q < 9; ++q) (coef_sel + (size_t)q * HW)[p] = (k == 2) ? kc[q].x : kc[q].y;
             }
         }
-        s += m;
+        if constexpr (MASKED) {
+            if (mask0[(size_t)b * HW + p] != 1.0f) { s += m; stat |= 1u << it; }
+        } else {
+            s += m;
+        }
     }
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    if constexpr (MASKED) {
+        // counts are integers: one ballot per pixel of the thread, popcount, four wave counts per block
+        __shared__ unsigned cred[4];
+        unsigned cnt = 0;
+#pragma unroll
+        for (int it = 0; it < (PA_TH * PA_TW) / 256; ++it) cnt += (unsigned)popcount64(wave_ballot((stat >> it) & 1u));
+        if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0 && sc == 0) cnt_partial[(size_t)b * gridDim.x + blockIdx.x] = (cred[0] + cred[1]) + (cred[2] + cred[3]);
+    } else {
+        __syncthreads();
+    }
     if (threadIdx.x == 0) partial_all[((size_t)sc * B + b) * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
@@ -352,14 +393,21 @@ __global__ __launch_bounds__(256) void pair_loss_kernel(const float* __restrict_
 // sample); sel and the selected-frame coefficients of the tile + 1-pixel halo are staged once in LDS
 // (every neighbour a pixel needs -- incl. the reflection fold -- lies in its 3x3 neighbourhood), then each
 // thread does the transposed SSIM stencil from LDS and the grid_sample / projection / depth backward.
+// MASKED (mask_dynamic): the loss is the mean over the static pixels of the whole minibatch (dpp.py:1068, 1075), so a
+// static pixel's term carries inv_n[0] / 4 = 1 / (4 N_static) (left on the device by the masked finalize) instead of
+// sample_w[b] / (H W) / 4, and a dynamic pixel's term carries 0: it is staged as "selected nothing" (sel = 255), which
+// removes it from every neighbour's transposed stencil and from its own L1 term.
 constexpr int LB_TH = 8, LB_TW = 64, LB_PH = LB_TH + 2, LB_PW = LB_TW + 2;
+template <bool MASKED = false>
 __global__ __launch_bounds__(256) void loss_bwd2_kernel(Pyramid pyr, const unsigned char* __restrict__ sel_all,
                                                         const float* __restrict__ coef_sel_all, const float* __restrict__ warped_all,
                                                         const float* __restrict__ target, const float* __restrict__ src_m1,
                                                         const float* __restrict__ src_p1, const float* __restrict__ Kinv,
                                                         const float* __restrict__ P, const float* __restrict__ sample_w,
                                                         float* __restrict__ ddisp_up_all, double* __restrict__ dP_partial, int B,
-                                                        int H, int W, float da, float db, int dmode, int tilesX) {
+                                                        int H, int W, float da, float db, int dmode, int tilesX,
+                                                        const float* __restrict__ mask0 = nullptr,
+                                                        const float* __restrict__ inv_n = nullptr) {
     // coefficients pixel-major, 10 floats per pixel as five pairs (alpha_0 alpha_1)(alpha_2 beta_0)(beta_1 beta_2)
     // (gamma_0 gamma_1)(gamma_2 -): a neighbour is five ds_read_b64 + five v_pk_fma instead of nine reads + nine FMAs
     // (40-byte stride: conflict-free for 8-byte reads)
@@ -376,13 +424,18 @@ __global__ __launch_bounds__(256) void loss_bwd2_kernel(Pyramid pyr, const unsig
     const float* coef = coef_sel_all + ((size_t)sc * B + b) * 9 * HW;
     const float* warped = warped_all + (size_t)sc * 2 * B * 3 * HW;
     float* ddisp_up = ddisp_up_all + (size_t)sc * B * HW;
-    const float wq = sample_w[b] / ((float)H * (float)W) / 4.f;
+    float wq;
+    if constexpr (MASKED) wq = inv_n[0] / 4.f;
+    else wq = sample_w[b] / ((float)H * (float)W) / 4.f;
     // ---- stage sel + coefficients (tile + halo; outside the image: sel = 255 -> never matches) -------------
     for (int e = threadIdx.x; e < LB_PH * LB_PW; e += 256) {
         const int r = e / LB_PW, c = e - r * LB_PW;
         const int yy = y0 - 1 + r, xx = x0 - 1 + c;
         const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-        const unsigned char sv = in ? sl[yy * W + xx] : (unsigned char)255;
+        unsigned char sv = in ? sl[yy * W + xx] : (unsigned char)255;
+        if constexpr (MASKED) {
+            if (in && mask0[(size_t)b * HW + yy * W + xx] == 1.0f) sv = (unsigned char)255;
+        }
         ss[e] = sv;
         const bool need = in && sv >= 2 && sv < 4;
         const unsigned o = need ? (unsigned)(yy * W + xx) : 0u;
@@ -437,15 +490,33 @@ __global__ __launch_bounds__(256) void loss_bwd2_kernel(Pyramid pyr, const unsig
             f32x2 acc[5];
 #pragma unroll
             for (int q = 0; q < 5; ++q) { acc[q].x = 0.f; acc[q].y = 0.f; }
+            [[maybe_unused]] float gn[3] = {0.f, 0.f, 0.f}, xw[3], yw[3];
+            if constexpr (MASKED) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    xw[c] = warped[((size_t)n * 3 + c) * HW + pi];
+                    yw[c] = target[((size_t)b * 3 + c) * HW + pi];
+                }
+            }
 #pragma unroll 1
             for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     const int e = (ly + dy) * LB_PW + lx + dx;
                     const float w1 = ss[e] == want ? (dy == 0 ? wy[0] : dy == 1 ? wy[1] : wy[2]) * wx[dx] : 0.f;
-                    const f32x2 ww = {w1, w1};
+                    if constexpr (MASKED) {
+                        // alpha + beta x + gamma y PER NEIGHBOUR, then summed (photo_grad_px says why): a masked selection is
+                        // thin and ragged, where summing the three parts over the neighbourhood first leaves their cancellation
+                        // (~1e3 x the result) to the end
+                        const f32x2 c0 = cs[e][0], c1 = cs[e][1], c2 = cs[e][2], c3 = cs[e][3], c4 = cs[e][4];
+                        gn[0] += w1 * (c0.x + c1.y * xw[0] + c3.x * yw[0]);
+                        gn[1] += w1 * (c0.y + c2.x * xw[1] + c3.y * yw[1]);
+                        gn[2] += w1 * (c1.x + c2.y * xw[2] + c4.x * yw[2]);
+                    } else {
+                        const f32x2 ww = {w1, w1};
 #pragma unroll
-                    for (int q = 0; q < 5; ++q) acc[q] = pk_fma(ww, cs[e][q], acc[q]);
+                        for (int q = 0; q < 5; ++q) acc[q] = pk_fma(ww, cs[e][q], acc[q]);
+                    }
                 }
             const float sA[3] = {acc[0].x, acc[0].y, acc[1].x}, sB[3] = {acc[1].y, acc[2].x, acc[2].y},
                         sC[3] = {acc[3].x, acc[3].y, acc[4].x};
@@ -466,7 +537,9 @@ __global__ __launch_bounds__(256) void loss_bwd2_kernel(Pyramid pyr, const unsig
             for (int c = 0; c < 3; ++c) {
                 const float xv = warped[((size_t)n * 3 + c) * HW + pi];
                 const float yv = target[((size_t)b * 3 + c) * HW + pi];
-                float g = sA[c] + sB[c] * xv + sC[c] * yv;
+                float g;
+                if constexpr (MASKED) g = gn[c];
+                else g = sA[c] + sB[c] * xv + sC[c] * yv;
                 if (own) g += (0.15f / 3.f) * (xv > yv ? 1.f : (xv < yv ? -1.f : 0.f));
                 g *= wq;
                 const float* pl = src + (size_t)c * HW;
@@ -998,11 +1071,13 @@ static int photo_automask_launch(const float* warped, const float* target, const
     const int nblk = clslam_automask_blocks(H, W);   // = number of 8 x 64 tiles
     const int tilesX = cdiv(W, PA_TW);
     if (coef_sel)
-        hipLaunchKernelGGL(photo_automask_kernel<true>, dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, warped, target,
-                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset);
+        hipLaunchKernelGGL((photo_automask_kernel<true, false>), dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, warped, target,
+                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset, (const float*)nullptr,
+                           (unsigned*)nullptr);
     else
-        hipLaunchKernelGGL(photo_automask_kernel<false>, dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, warped, target,
-                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset);
+        hipLaunchKernelGGL((photo_automask_kernel<false, false>), dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, warped, target,
+                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset, (const float*)nullptr,
+                           (unsigned*)nullptr);
     return check_launch("photo_automask_pyramid");
 }
 
@@ -1041,9 +1116,9 @@ extern "C" int clslam_loss_bwd2_pyramid(const float* const* disp, const unsigned
     depth_mode(min_depth, max_depth, &a, &b, &mode);
     if (!batch) return CLSLAM_OK;
     const int tilesX = cdiv(W, LB_TW);
-    hipLaunchKernelGGL(loss_bwd2_kernel, dim3(clslam_loss_bwd2_blocks(H, W), batch, 4), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(loss_bwd2_kernel<false>, dim3(clslam_loss_bwd2_blocks(H, W), batch, 4), dim3(256), 0, (hipStream_t)stream,
                        make_pyramid(disp, H, W), sel, coef_sel, warped, target, src_m1, src_p1, inv_k, proj, sample_w, ddisp_up,
-                       dp_partial, batch, H, W, a, b, mode, tilesX);
+                       dp_partial, batch, H, W, a, b, mode, tilesX, (const float*)nullptr, (const float*)nullptr);
     return check_launch("loss_bwd2_pyramid");
 }
 
@@ -1392,4 +1467,442 @@ extern "C" int clslam_pair_loss_finalize(const float* partial, int nblk, const f
     hipLaunchKernelGGL(clslam::pair_loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nblk, disp, rgb0, means,
                        si_partial, pose, dist, sample_w, smooth_w, n_smooth, losses, batch, H, W, smooth_scale, vel_scale);
     return check_launch("pair_loss_finalize");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// mask_dynamic = True (dpp.py:1063-1090 and 1148-1176 with the masks of the dataset): "potentially dynamic" pixels leave
+// the loss.  inputs['mask', 0, s] (B,1,h_s,w_s) float, one plane per scale as the dataset builds it; a pixel is STATIC
+// iff its value != 1.0f ((1 - m).type(torch.bool): 0.5 and 2.0 are static, only an exact 1 is dynamic).
+//   * reprojection (every scale uses the scale-0 mask): sum over the static pixels of ALL samples / N_static, no sample
+//     weights (photo_automask_kernel<., true> above writes the sums and counts, loss_bwd2_kernel<true> is the backward);
+//   * smoothness, default mode: masked_select flattens the batch, so term i < B is the i-th static element of the cropped
+//     x plane (B,1,h,w-1) plus the i-th static element of the cropped y plane (B,1,h-1,w) -- found by smooth_locate_kernel
+//     -- weighted by smooth_w[i]; the reference's second masked_select then averages that scalar over mask[i], which is
+//     the scalar itself when sample i has a static element in both cropped planes and NaN otherwise.  Supported layout:
+//     all B elements lie in sample 0 (else the term is written as NaN: the reference raises IndexError or reads sample 1);
+//   * smoothness, reference_quirks = False: per sample the masked mean of the x terms + the masked mean of the y terms.
+// No floating-point atomics, fixed reduction orders; the counts are unsigned integers converted once.
+namespace clslam {
+
+struct MaskPtrs { const float* m[4]; };
+
+__device__ __forceinline__ bool mask_static(float m) { return m != 1.0f; }
+
+// loc [4][2][2 * B] int (scale, direction x / y): [i < B] pixel index (y * w + x, full plane) of the i-th static element of
+// sample 0's cropped plane in flat order or -1 when it has fewer; [B + b] 1 if sample b has a static element there, else 0.
+// grid (B, 2, 4).  A block scans its sample in chunks of 256 elements: one ballot per wave, the prefix popcount ranks the
+// static lanes, and the scan ends as soon as the block has what it needs (B positions for sample 0, one hit otherwise).
+__global__ __launch_bounds__(256) void smooth_locate_kernel(MaskPtrs mk, int* __restrict__ loc, int B, int H, int W) {
+    __shared__ int wcnt[4];
+    const int b = blockIdx.x, dir = blockIdx.y, sc = blockIdx.z;
+    const int h = H >> sc, w = W >> sc;
+    const float* m = mk.m[sc] + (size_t)b * h * w;
+    const int cw = dir == 0 ? w - 1 : w;                         // width of the cropped plane
+    const int n = dir == 0 ? h * (w - 1) : (h - 1) * w;
+    const int need = b == 0 ? B : 1;
+    int* out = loc + (size_t)(sc * 2 + dir) * 2 * B;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int found = 0;                                               // block-uniform
+    for (int e0 = 0; e0 < n && found < need; e0 += 256) {
+        const int e = e0 + (int)threadIdx.x;
+        int p = 0;
+        bool st = false;
+        if (e < n) {
+            const int y = e / cw, x = e - y * cw;
+            p = y * w + x;
+            st = mask_static(m[p]);
+        }
+        const unsigned long long bal = wave_ballot(st);
+        if (lane == 0) wcnt[wave] = popcount64(bal);
+        __syncthreads();
+        int base = found;
+        for (int k = 0; k < wave; ++k) base += wcnt[k];
+        const int rank = base + popcount64(bal & ((1ull << lane) - 1ull));
+        if (b == 0 && st && rank < B) out[rank] = p;
+        found += (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+        __syncthreads();
+    }
+    if (b == 0)
+        for (int i = found + (int)threadIdx.x; i < B; i += 256) out[i] = -1;
+    if (threadIdx.x == 0) out[B + b] = found > 0 ? 1 : 0;
+}
+
+struct MaskedFinalizeArgs {
+    FinalizeArgs a;
+    const unsigned* cnt;      // [B][nblk] static pixels per tile
+    const int* loc;           // smooth_locate_kernel's output, or NULL when n_smooth == 0
+    float* mstat;             // [2]: 1 / N_static (read by loss_bwd2_kernel<true>), N_static
+};
+
+// loss_finalize_kernel for the masked loss: same 18 slots, same smooth_aux layout.  One block of 256 threads.
+__global__ __launch_bounds__(256) void loss_finalize_masked_kernel(MaskedFinalizeArgs ma) {
+    const FinalizeArgs& a = ma.a;
+    __shared__ float s_rl[4 * FIN_MAXB];      // per-sample sums over the static pixels (unweighted)
+    __shared__ float s_sm[4 * FIN_MAXB];
+    __shared__ float s_ds[4 * FIN_MAXB];
+    __shared__ float s_vel[FIN_MAXB];
+    __shared__ float s_mean[4 * FIN_MAXB];
+    __shared__ unsigned s_cnt[256];
+    const int tid = threadIdx.x;
+    {
+        unsigned c = 0;
+        for (int k = tid; k < a.B * a.nblk; k += 256) c += ma.cnt[k];
+        s_cnt[tid] = c;
+    }
+    for (int pr = tid; pr < 4 * a.B; pr += 256) {
+        const int s = pr / a.B, b = pr - s * a.B;
+        float sum = 0.f;
+        for (int k = 0; k < DM_CHUNKS; ++k) sum += a.means[s][(size_t)b * DM_CHUNKS + k];
+        s_mean[pr] = sum / (float)((a.H >> s) * (a.W >> s));
+    }
+    __syncthreads();
+    for (int pr0 = 0; pr0 < 4 * a.B; pr0 += 32) {
+        const int pr = pr0 + (tid >> 3), kl = tid & 7;
+        const bool live = pr < 4 * a.B;
+        const int s = live ? pr / a.B : 0, b = live ? pr - s * a.B : 0;
+        float sum = 0.f;
+        if (live)
+            for (int k = kl; k < a.nblk; k += 8) sum += a.partial[s][(size_t)b * a.nblk + k];
+        sum += wave_shfl_xor(sum, 1);
+        sum += wave_shfl_xor(sum, 2);
+        sum += wave_shfl_xor(sum, 4);
+        if (live && kl == 0) s_rl[pr] = sum;
+    }
+    // smoothness, reference quirk on the masked planes: term i = the i-th static element of each cropped plane (sample 0)
+    for (int pr = tid; pr < 4 * a.n_smooth; pr += 256) {
+        const int s = pr / a.n_smooth, i = pr - s * a.n_smooth;
+        const int h = a.H >> s, w = a.W >> s;
+        float* aux = a.smooth_aux + (size_t)s * (2 + 2 * a.n_smooth);
+        const int* lx = ma.loc + (size_t)(s * 2 + 0) * 2 * a.B;
+        const int* ly = ma.loc + (size_t)(s * 2 + 1) * 2 * a.B;
+        const int px = lx[i], py = ly[i];
+        // dpp.py:1172-1174: the scalar averaged over mask[i] -- sample i needs a static element in both cropped planes
+        const bool ok = px >= 0 && py >= 0 && px + 1 < h * w && py + w < h * w && lx[a.B + i] != 0 && ly[a.B + i] != 0;
+        if (!ok) {
+            s_sm[pr] = __uint_as_float(0x7fc00000u);
+            s_ds[pr] = 0.f;
+            aux[2 + i] = 0.f;
+            aux[2 + a.n_smooth + i] = 0.f;
+            continue;
+        }
+        const float coefs = a.smooth_scale / (float)(1 << s) / 4.f;
+        const float* dp = a.disp[s];                              // sample 0
+        const float m0 = s_mean[s * a.B + 0] + 1e-7f;
+        const float ax = dp[px] / m0, bxv = dp[px + 1] / m0;      // norm_disp (dpp.py:1087-1088)
+        const float ay = dp[py] / m0, byv = dp[py + w] / m0;
+        float gix = 0.f, giy = 0.f;
+        for (int c = 0; c < 3; ++c) {
+            const float* im = a.rgb0[s] + (size_t)c * h * w;
+            gix += fabsf(im[px] - im[px + 1]);
+            giy += fabsf(im[py] - im[py + w]);
+        }
+        const float ex = expf(-(gix / 3.f)), ey = expf(-(giy / 3.f));
+        s_sm[pr] = (fabsf(ax - bxv) * ex + fabsf(ay - byv) * ey) * a.smooth_w[i];
+        const float sgx = (ax > bxv) ? 1.f : (ax < bxv ? -1.f : 0.f);
+        const float sgy = (ay > byv) ? 1.f : (ay < byv ? -1.f : 0.f);
+        const float gxs = coefs * a.smooth_w[i] * ex * sgx;
+        const float gys = coefs * a.smooth_w[i] * ey * sgy;
+        aux[2 + i] = gxs;
+        aux[2 + a.n_smooth + i] = gys;
+        s_ds[pr] = gxs * (dp[px] - dp[px + 1]) + gys * (dp[py] - dp[py + w]);
+    }
+    if (a.vel_scale > 0.f) {
+        for (int b = tid; b < a.B; b += 256) {
+            float acc = 0.f;
+            for (int fi = 0; fi < 2; ++fi) {
+                const float* t = a.pose + ((size_t)fi * a.B + b) * 12 + 3;
+                const float nrm = sqrtf(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+                const double gt = fabs(fi == 0 ? a.dist0[b] : a.dist1[b]);
+                acc = (float)((double)acc + fabs((double)nrm - gt));   // fp32 += fp64 (dpp.py:1142)
+            }
+            s_vel[b] = (a.vel_scale * (acc / 2.f)) * a.sample_w[b];
+        }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    unsigned n_static = 0;
+    for (int k = 0; k < 256; ++k) n_static += s_cnt[k];
+    const float nf = (float)n_static;
+    ma.mstat[0] = 1.f / nf;
+    ma.mstat[1] = nf;
+    float total = 0.f;
+    for (int s = 0; s < 4; ++s) {
+        const int h = a.H >> s, w = a.W >> s;
+        float rs = 0.f, sm = 0.f, dsum = 0.f;
+        for (int b = 0; b < a.B; ++b) rs += s_rl[s * a.B + b];
+        const float rl = rs / nf;                                // to_optimize.mean(): 0 / 0 = NaN without a static pixel
+        for (int i = 0; i < a.n_smooth; ++i) { sm += s_sm[s * a.n_smooth + i]; dsum += s_ds[s * a.n_smooth + i]; }
+        if (a.n_smooth > 0) {
+            float* aux = a.smooth_aux + (size_t)s * (2 + 2 * a.n_smooth);
+            const float inv0 = 1.f / (s_mean[s * a.B + 0] + 1e-7f);
+            aux[0] = inv0;
+            aux[1] = dsum * inv0 * inv0 / (float)(h * w);
+        }
+        const float reg = a.smooth_scale / (float)(1 << s) * sm;
+        const float loss = rl + reg;
+        a.losses[s * 4 + 0] = rl; a.losses[s * 4 + 1] = sm; a.losses[s * 4 + 2] = reg; a.losses[s * 4 + 3] = loss;
+        total += loss;
+    }
+    total = total / 4.f;
+    float vel = 0.f;
+    if (a.vel_scale > 0.f) {
+        for (int b = 0; b < a.B; ++b) vel += s_vel[b];
+        total += vel;
+    }
+    a.losses[16] = vel;
+    a.losses[17] = total;
+}
+
+// Gradient of the positioned quirk terms, ADDED to dz of sample 0 (clslam_disp_grad_pyramid ran with n_smooth = 0):
+// d/d norm_disp of term i sits at its two x pixels (px, px + 1) and its two y pixels (py, py + w); the mean-normalisation
+// feedback aux[1] reaches every pixel of sample 0.  grid (cdiv(H W, 256), 4).
+__global__ __launch_bounds__(256) void smooth_pos_bwd_kernel(Pyramid pyr, const float* __restrict__ aux_all,
+                                                             const int* __restrict__ loc, int n_smooth, SiDz out, int B) {
+    const int sc = blockIdx.y;
+    const int h = pyr.h[sc], w = pyr.w[sc];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= h * w) return;
+    const float* aux = aux_all + (size_t)sc * (2 + 2 * n_smooth);
+    const int* lx = loc + (size_t)(sc * 2 + 0) * 2 * B;
+    const int* ly = loc + (size_t)(sc * 2 + 1) * 2 * B;
+    const float inv0 = aux[0], fb = aux[1];
+    float D = 0.f;
+    for (int i = 0; i < n_smooth; ++i) {
+        const int px = lx[i], py = ly[i];
+        const float gxs = aux[2 + i], gys = aux[2 + n_smooth + i];
+        if (px >= 0) {
+            if (p == px) D += gxs;
+            if (p == px + 1) D -= gxs;
+        }
+        if (py >= 0) {
+            if (p == py) D += gys;
+            if (p == py + w) D -= gys;
+        }
+    }
+    const float d = pyr.disp[sc][p];                             // sample 0
+    si_accumulate(out.dz[sc] + p, (inv0 * D - fb) * d * (1.f - d));
+}
+
+// Masked per-sample smoothness (reference_quirks = False with mask_dynamic): chunked sums of the x and of the y terms over
+// the static elements of the cropped planes, and how many there are.  partial [4][B][SI_CHUNKS][2], cnt likewise (unsigned).
+__global__ __launch_bounds__(256) void smooth_intended_masked_fwd_kernel(Pyramid pyr, SiPtrs im, MaskPtrs mk,
+                                                                         float* __restrict__ partial, unsigned* __restrict__ cnt,
+                                                                         int B) {
+    __shared__ float red[2][4];
+    __shared__ unsigned cred[2][4];
+    const int b = blockIdx.y, sc = blockIdx.z;
+    const int h = pyr.h[sc], w = pyr.w[sc], hw = h * w;
+    const float* d = pyr.disp[sc] + (size_t)b * hw;
+    const float* img = im.rgb0[sc] + (size_t)b * 3 * hw;
+    const float* m = mk.m[sc] + (size_t)b * hw;
+    const int per = (hw + SI_CHUNKS - 1) / SI_CHUNKS;
+    const int p0 = blockIdx.x * per, p1 = min(hw, p0 + per);
+    float sx = 0.f, sy = 0.f;
+    unsigned cx = 0, cy = 0;                                     // per wave
+    for (int q = p0; q < p1; q += 256) {                         // block-uniform trip count: the ballots see whole waves
+        const int p = q + (int)threadIdx.x;
+        bool ux = false, uy = false;
+        if (p < p1 && mask_static(m[p])) {
+            const int y = p / w, x = p - y * w;
+            ux = x + 1 < w;
+            uy = y + 1 < h;
+            if (ux) sx += fabsf(d[p] - d[p + 1]) * si_edge_weight(img, hw, p, p + 1);
+            if (uy) sy += fabsf(d[p] - d[p + w]) * si_edge_weight(img, hw, p, p + w);
+        }
+        cx += (unsigned)popcount64(wave_ballot(ux));
+        cy += (unsigned)popcount64(wave_ballot(uy));
+    }
+    sx = wave_sum(sx);
+    sy = wave_sum(sy);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = sx; red[1][threadIdx.x >> 6] = sy;
+        cred[0][threadIdx.x >> 6] = cx; cred[1][threadIdx.x >> 6] = cy;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const size_t o = (((size_t)sc * B + b) * SI_CHUNKS + blockIdx.x) * 2 + threadIdx.x;
+        partial[o] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+        cnt[o] = (cred[threadIdx.x][0] + cred[threadIdx.x][1]) + (cred[threadIdx.x][2] + cred[threadIdx.x][3]);
+    }
+}
+
+// one thread: 4 x B terms, fixed order.  aux [4][B][4] = (inv, Tx / nx + Ty / ny, 1 / nx, 1 / ny); a sample without a static
+// element in a cropped plane gives 0 / 0 = NaN like the empty mean of dpp.py:1174.
+__global__ void smooth_intended_masked_finalize_kernel(const float* __restrict__ partial, const unsigned* __restrict__ cnt,
+                                                       const float* __restrict__ means_all, const float* __restrict__ sample_w,
+                                                       float* __restrict__ losses, float* __restrict__ aux, int B, int H, int W,
+                                                       float smooth_scale) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float add_total = 0.f;
+    for (int s = 0; s < 4; ++s) {
+        const int hw = (H >> s) * (W >> s);
+        float sm = 0.f;
+        for (int b = 0; b < B; ++b) {
+            float m = 0.f, Tx = 0.f, Ty = 0.f;
+            unsigned nx = 0, ny = 0;
+            for (int k = 0; k < DM_CHUNKS; ++k) m += means_all[((size_t)s * B + b) * DM_CHUNKS + k];
+            for (int k = 0; k < SI_CHUNKS; ++k) {
+                const size_t o = (((size_t)s * B + b) * SI_CHUNKS + k) * 2;
+                Tx += partial[o]; Ty += partial[o + 1];
+                nx += cnt[o]; ny += cnt[o + 1];
+            }
+            const float inv = 1.f / (m / (float)hw + 1e-7f);
+            const float T = Tx / (float)nx + Ty / (float)ny;
+            float* o = aux + ((size_t)s * B + b) * 4;
+            o[0] = inv; o[1] = T; o[2] = 1.f / (float)nx; o[3] = 1.f / (float)ny;
+            sm += (inv * T) * sample_w[b];
+        }
+        const float reg = smooth_scale / (float)(1 << s) * sm;
+        losses[s * 4 + 1] = sm;
+        losses[s * 4 + 2] = reg;
+        losses[s * 4 + 3] += reg;
+        add_total += reg;
+    }
+    losses[17] += add_total / 4.f;
+}
+
+__global__ __launch_bounds__(256) void smooth_intended_masked_bwd_kernel(Pyramid pyr, SiPtrs im, MaskPtrs mk,
+                                                                         const float* __restrict__ aux,
+                                                                         const float* __restrict__ sample_w, SiDz out, int B,
+                                                                         float smooth_scale) {
+    const int b = blockIdx.y, sc = blockIdx.z;
+    const int h = pyr.h[sc], w = pyr.w[sc], hw = h * w;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= hw) return;
+    const float* d = pyr.disp[sc] + (size_t)b * hw;
+    const float* img = im.rgb0[sc] + (size_t)b * 3 * hw;
+    const float* m = mk.m[sc] + (size_t)b * hw;
+    const float* a4 = aux + ((size_t)sc * B + b) * 4;
+    const float inv = a4[0], T = a4[1], nx = a4[2], ny = a4[3];
+    const int y = p / w, x = p - y * w;
+    const float dp = d[p];
+    auto sgn = [](float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); };
+    const bool own = mask_static(m[p]);                          // an edge belongs to its left / upper pixel's mask value
+    float g = 0.f;
+    if (x + 1 < w && own) g += sgn(dp - d[p + 1]) * si_edge_weight(img, hw, p, p + 1) * nx;
+    if (x >= 1 && mask_static(m[p - 1])) g -= sgn(d[p - 1] - dp) * si_edge_weight(img, hw, p - 1, p) * nx;
+    if (y + 1 < h && own) g += sgn(dp - d[p + w]) * si_edge_weight(img, hw, p, p + w) * ny;
+    if (y >= 1 && mask_static(m[p - w])) g -= sgn(d[p - w] - dp) * si_edge_weight(img, hw, p - w, p) * ny;
+    const float coef = smooth_scale / (float)(1 << sc) / 4.f * sample_w[b];
+    const float dl = coef * (inv * g - T * inv * inv / (float)hw);
+    si_accumulate(out.dz[sc] + (size_t)b * hw + p, dp * (1.f - dp) * dl);
+}
+
+}  // namespace clslam
+
+static clslam::MaskPtrs make_mask_ptrs(const float* const* mask) {
+    clslam::MaskPtrs mk;
+    for (int s = 0; s < 4; ++s) mk.m[s] = mask[s];
+    return mk;
+}
+
+extern "C" int clslam_photo_automask_pyramid_masked(const float* warped, const float* target, const float* idmap,
+                                                    const float* noise, unsigned long long seed, unsigned long long offset,
+                                                    const float* mask0, unsigned char* sel, float* coef_sel, float* partial,
+                                                    unsigned* cnt_partial, int batch, int H, int W, void* stream) {
+    CLSLAM_REQUIRE(warped && target && idmap && sel && partial && mask0 && cnt_partial && H >= 2 && W >= 2,
+                   "photo_automask_pyramid_masked: bad args");
+    CLSLAM_REQUIRE(noise || seed != 0, "photo_automask_pyramid_masked: a noise tensor or a non-zero seed");
+    if (!batch) return CLSLAM_OK;
+    if (noise) seed = offset = 0ull;
+    const int nblk = clslam_automask_blocks(H, W);
+    const int tilesX = cdiv(W, PA_TW);
+    if (coef_sel)
+        hipLaunchKernelGGL((photo_automask_kernel<true, true>), dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, warped, target,
+                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset, mask0, cnt_partial);
+    else
+        hipLaunchKernelGGL((photo_automask_kernel<false, true>), dim3(nblk, batch, 4), dim3(256), 0, (hipStream_t)stream, warped, target,
+                           idmap, noise, sel, coef_sel, partial, batch, H, W, tilesX, seed, offset, mask0, cnt_partial);
+    return check_launch("photo_automask_pyramid_masked");
+}
+
+extern "C" int clslam_smooth_locate(const float* const* mask, int* loc, int batch, int H, int W, void* stream) {
+    CLSLAM_REQUIRE(mask && loc && mask[0] && mask[1] && mask[2] && mask[3], "smooth_locate: null");
+    CLSLAM_REQUIRE(H % 8 == 0 && W % 8 == 0 && (H >> 3) >= 2 && (W >> 3) >= 2 && (size_t)H * W < ((size_t)1 << 30),
+                   "smooth_locate: H, W must be multiples of 8, at least 16");
+    if (!batch) return CLSLAM_OK;
+    hipLaunchKernelGGL(clslam::smooth_locate_kernel, dim3(batch, 2, 4), dim3(256), 0, (hipStream_t)stream, make_mask_ptrs(mask), loc,
+                       batch, H, W);
+    return check_launch("smooth_locate");
+}
+
+extern "C" int clslam_loss_finalize_masked(const clslam_loss_desc* d, const unsigned* cnt_partial, const int* loc, float* mstat,
+                                           void* stream) {
+    CLSLAM_REQUIRE(d && d->losses && d->pose && d->sample_w && cnt_partial && mstat, "loss_finalize_masked: null");
+    CLSLAM_REQUIRE(d->n_smooth == 0 || (d->smooth_w && d->smooth_aux && loc && d->n_smooth == d->batch),
+                   "loss_finalize_masked: the masked smoothness has one term per sample and needs smooth_w, smooth_aux and loc");
+    CLSLAM_REQUIRE(d->batch >= 1 && d->batch <= FIN_MAXB, "loss_finalize_masked: batch > %d", FIN_MAXB);
+    CLSLAM_REQUIRE(d->H % 8 == 0 && d->W % 8 == 0 && (d->H >> 3) >= 2 && (d->W >> 3) >= 2, "loss_finalize_masked: bad size");
+    clslam::MaskedFinalizeArgs ma;
+    FinalizeArgs& a = ma.a;
+    for (int s = 0; s < 4; ++s) { a.partial[s] = d->partial[s]; a.disp[s] = d->disp[s]; a.rgb0[s] = d->rgb0[s]; a.means[s] = d->means[s]; }
+    a.pose = d->pose; a.dist0 = d->dist0; a.dist1 = d->dist1; a.sample_w = d->sample_w; a.smooth_w = d->smooth_w;
+    a.losses = d->losses; a.smooth_aux = d->smooth_aux; a.B = d->batch; a.nblk = d->nblk; a.H = d->H; a.W = d->W;
+    a.n_smooth = d->n_smooth; a.smooth_scale = d->smooth_scale; a.vel_scale = d->vel_scale;
+    ma.cnt = cnt_partial; ma.loc = loc; ma.mstat = mstat;
+    hipLaunchKernelGGL(clslam::loss_finalize_masked_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ma);
+    return check_launch("loss_finalize_masked");
+}
+
+extern "C" int clslam_loss_bwd2_pyramid_masked(const float* const* disp, const unsigned char* sel, const float* coef_sel,
+                                               const float* warped, const float* target, const float* src_m1, const float* src_p1,
+                                               const float* inv_k, const float* proj, const float* mask0, const float* inv_n,
+                                               float* ddisp_up, double* dp_partial, int batch, int H, int W, float min_depth,
+                                               float max_depth, void* stream) {
+    CLSLAM_REQUIRE(disp && sel && coef_sel && warped && target && src_m1 && src_p1 && inv_k && proj && mask0 && inv_n && ddisp_up &&
+                   dp_partial, "loss_bwd2_pyramid_masked: null");
+    float a, b; int mode;
+    depth_mode(min_depth, max_depth, &a, &b, &mode);
+    if (!batch) return CLSLAM_OK;
+    const int tilesX = cdiv(W, LB_TW);
+    hipLaunchKernelGGL(loss_bwd2_kernel<true>, dim3(clslam_loss_bwd2_blocks(H, W), batch, 4), dim3(256), 0, (hipStream_t)stream,
+                       make_pyramid(disp, H, W), sel, coef_sel, warped, target, src_m1, src_p1, inv_k, proj, (const float*)nullptr,
+                       ddisp_up, dp_partial, batch, H, W, a, b, mode, tilesX, mask0, inv_n);
+    return check_launch("loss_bwd2_pyramid_masked");
+}
+
+extern "C" int clslam_smooth_pos_bwd(const float* const* disp, const float* smooth_aux, const int* loc, int n_smooth,
+                                     float* const* dz, int batch, int H, int W, void* stream) {
+    CLSLAM_REQUIRE(disp && smooth_aux && loc && dz && n_smooth >= 1 && n_smooth == batch, "smooth_pos_bwd: bad args");
+    CLSLAM_REQUIRE(H % 8 == 0 && W % 8 == 0 && (H >> 3) >= 2 && (W >> 3) >= 2, "smooth_pos_bwd: bad size");
+    clslam::SiDz out;
+    for (int s = 0; s < 4; ++s) out.dz[s] = dz[s];
+    hipLaunchKernelGGL(clslam::smooth_pos_bwd_kernel, dim3(clslam::cdiv(H * W, 256), 4), dim3(256), 0, (hipStream_t)stream,
+                       make_pyramid(disp, H, W), smooth_aux, loc, n_smooth, out, batch);
+    return check_launch("smooth_pos_bwd");
+}
+
+extern "C" int clslam_smooth_intended_masked_fwd(const float* const* disp, const float* const* rgb0, const float* const* mask,
+                                                 float* partial, unsigned* cnt, int batch, int H, int W, void* stream) {
+    CLSLAM_REQUIRE(disp && rgb0 && mask && partial && cnt && (H >> 3) >= 2 && (W >> 3) >= 2, "smooth_intended_masked_fwd: bad args");
+    if (!batch) return CLSLAM_OK;
+    clslam::SiPtrs im;
+    for (int s = 0; s < 4; ++s) im.rgb0[s] = rgb0[s];
+    hipLaunchKernelGGL(clslam::smooth_intended_masked_fwd_kernel, dim3(clslam::SI_CHUNKS, batch, 4), dim3(256), 0, (hipStream_t)stream,
+                       make_pyramid(disp, H, W), im, make_mask_ptrs(mask), partial, cnt, batch);
+    return check_launch("smooth_intended_masked_fwd");
+}
+
+extern "C" int clslam_smooth_intended_masked_finalize(const float* partial, const unsigned* cnt, const float* means,
+                                                      const float* sample_w, float* losses, float* aux, int batch, int H, int W,
+                                                      float smooth_scale, void* stream) {
+    CLSLAM_REQUIRE(partial && cnt && means && sample_w && losses && aux, "smooth_intended_masked_finalize: null");
+    if (!batch) return CLSLAM_OK;
+    hipLaunchKernelGGL(clslam::smooth_intended_masked_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, cnt, means,
+                       sample_w, losses, aux, batch, H, W, smooth_scale);
+    return check_launch("smooth_intended_masked_finalize");
+}
+
+extern "C" int clslam_smooth_intended_masked_bwd(const float* const* disp, const float* const* rgb0, const float* const* mask,
+                                                 const float* aux, const float* sample_w, float* const* dz, int batch, int H, int W,
+                                                 float smooth_scale, void* stream) {
+    CLSLAM_REQUIRE(disp && rgb0 && mask && aux && sample_w && dz && (H >> 3) >= 2 && (W >> 3) >= 2, "smooth_intended_masked_bwd: bad args");
+    if (!batch) return CLSLAM_OK;
+    clslam::SiPtrs im;
+    clslam::SiDz out;
+    for (int s = 0; s < 4; ++s) { im.rgb0[s] = rgb0[s]; out.dz[s] = dz[s]; }
+    hipLaunchKernelGGL(clslam::smooth_intended_masked_bwd_kernel, dim3(clslam::cdiv(H * W, 256), batch, 4), dim3(256), 0,
+                       (hipStream_t)stream, make_pyramid(disp, H, W), im, make_mask_ptrs(mask), aux, sample_w, out, batch,
+                       smooth_scale);
+    return check_launch("smooth_intended_masked_bwd");
 }

@@ -188,9 +188,6 @@ class DepthPosePrediction:
         if use_online:
             raise ValueError('use_online (dual network) is never enabled by the reference SLAM driver '
                              '(slam/slam.py:39) and is not part of the accelerated path')
-        if self.mask_dynamic:
-            raise ValueError('mask_dynamic=True is the pre-training configuration; the accelerated path implements '
-                             'the adaptation configuration (mask_dynamic=False, config_adapt.yaml:26)')
         if tuple(self.scales) != (0, 1, 2, 3):
             raise ValueError('The accelerated path implements scales=(0, 1, 2, 3)')
         # =================================================
@@ -207,7 +204,8 @@ class DepthPosePrediction:
         self.engine = Engine(self.height, self.width, self.device, min_depth=self.min_depth, max_depth=self.max_depth,
                              disparity_smoothness=self.disparity_smoothness,
                              velocity_loss_scaling=self.velocity_loss_scaling,
-                             reference_quirks=reference_quirks)   # False: opt-in per-sample smoothness
+                             reference_quirks=reference_quirks,   # False: opt-in per-sample smoothness
+                             mask_dynamic=bool(self.mask_dynamic))  # dpp.py:1063-1090: inputs['mask', 0, s] == 1 leaves the loss
         for m in self.models.values():
             m.to(self.device)
         self.engine.bind(self.models)
@@ -269,6 +267,9 @@ class DepthPosePrediction:
         ``adapt`` with ITS contiguous shard of the (online + replay) minibatch; the rank whose shard
         starts at 0 holds the online sample.  Loss terms use the global batch size, the flat
         gradient arena is sum-all-reduced once per step, Adam runs identically on every rank."""
+        if self.mask_dynamic:
+            raise ValueError('enable_data_parallel with mask_dynamic=True: the masked reprojection loss is one mean over the static '
+                             'pixels of the WHOLE minibatch, which needs a collective over the ranks\' counts that is not built')
         import torch.distributed as dist
         if not dist.is_initialized():
             raise RuntimeError('torch.distributed is not initialised')
@@ -372,8 +373,8 @@ class DepthPosePrediction:
         """Compute the validation loss (dpp.py:321-342): eval mode, the forward-only _process_batch per batch, the mean of
         losses['loss'].  data_loader: any iterable of batches as adapt() takes them; None builds (once) the validation loader like
         dpp.py:871-904, which needs the reference's `datasets` package.  The loss scalars stay on the device and are read back
-        together at the end.  save_val_depth needs the reference's plotting save_prediction, which is not provided: it is skipped
-        with one warning."""
+        together at the end.  save_val_depth: validate() does not call save_prediction (dpp.py:336-337 does); it says so with
+        one warning and writes nothing -- call save_prediction(inputs, outputs) on the batches to keep."""
         if not self.is_trained:
             warnings.warn('The model has not been trained yet.', RuntimeWarning)
         if data_loader is None:
@@ -381,7 +382,7 @@ class DepthPosePrediction:
                 self.val_loader = self._validation_loader()
             data_loader = self.val_loader
         if self.save_val_depth and self.save_val_depth_batches > 0:
-            warnings.warn('save_val_depth: save_prediction (matplotlib plots) is not provided; no depth image is saved',
+            warnings.warn('save_val_depth: validate() does not call save_prediction; no depth image is saved',
                           RuntimeWarning)
         self._set_eval()
         self.engine.pack_if_needed()
@@ -615,6 +616,9 @@ class DepthPosePrediction:
             image_1 = image_1.unsqueeze(dim=0)
         kw = {}
         if return_loss:
+            if self.mask_dynamic:
+                # the reference raises KeyError here: _compute_loss reads inputs['mask', 0, 0], which this call never supplies
+                raise ValueError('predict_from_images(return_loss=True) with mask_dynamic=True: the call takes no mask')
             if camera_matrix is None or inv_camera_matrix is None:
                 raise ValueError('predict_from_images(return_loss=True) needs camera_matrix and inv_camera_matrix')
             vel = self.velocity_loss_scaling is not None and self.velocity_loss_scaling > 0
@@ -925,6 +929,8 @@ class DepthPosePrediction:
     UPLOAD_FIRST = [('rgb_aug', 0, 0), ('rgb_aug', -1, 0), ('rgb_aug', 1, 0)]
     UPLOAD_REST = [('camera_matrix', 0), ('inv_camera_matrix', 0), ('relative_distance', 0), ('relative_distance', 1),
                    ('rgb', -1, 0), ('rgb', 1, 0), ('rgb', 0, 0), ('rgb', 0, 1), ('rgb', 0, 2), ('rgb', 0, 3)]
+    # read with mask_dynamic=True only (dpp.py:1066, 1081): uploaded with the entries the path reads in that mode
+    UPLOAD_MASKS = [('mask', 0, 0), ('mask', 0, 1), ('mask', 0, 2), ('mask', 0, 3)]
 
     def _upload(self, inputs: Dict[Any, Tensor]):
         """Move the caller's dict to the device in place like dpp.py:916-917, asynchronously: the copies run on their own
@@ -935,8 +941,9 @@ class DepthPosePrediction:
         has been enqueued, so that their ~0.15 ms of host-side copy calls sit behind GPU work instead of in front of it --
         or None when nothing had to move."""
         dev = self.device
-        todo = [k for k in self.UPLOAD_FIRST + self.UPLOAD_REST if k in inputs and inputs[k].device != dev]
-        known = set(self.UPLOAD_FIRST + self.UPLOAD_REST)
+        read = self.UPLOAD_FIRST + self.UPLOAD_REST + (self.UPLOAD_MASKS if self.mask_dynamic else [])
+        todo = [k for k in read if k in inputs and inputs[k].device != dev]
+        known = set(read)
         extra = [k for k in inputs if self.upload_all_inputs and k not in known
                  and isinstance(inputs[k], Tensor) and inputs[k].device != dev]
         if not todo and not extra:

@@ -309,6 +309,54 @@ typedef struct clslam_loss_desc {
     float smooth_scale, vel_scale;
 } clslam_loss_desc;
 int clslam_loss_finalize(const clslam_loss_desc* desc, void* stream);
+/* ---- mask_dynamic = True: the masked loss (additive entry points, ABI 114) --------------------------------------------------
+ * masks: inputs['mask', 0, s] as (B,h_s,w_s) float planes, one per scale as the dataset builds them.  A pixel is STATIC iff its
+ * value != 1.0f ((1 - m).type(torch.bool), dpp.py:1066-1067 and 1081-1082: 0.5 and 2.0 are static, only an exact 1 is dynamic).
+ * Reprojection (dpp.py:1063-1076): every scale uses the scale-0 mask; reprojection_loss/scale_s = sum over the static pixels of
+ * ALL samples of the per-pixel minimum / N_static; sample_w is NOT applied to it (it still weights smoothness and velocity).
+ * Smoothness, default mode (dpp.py:1080-1090 into 1148-1176): masked_select flattens the batch, so term i < B is the i-th static
+ * element of the cropped x plane (B,1,h,w-1) plus the i-th static element of the cropped y plane (B,1,h-1,w), weighted by
+ * smooth_w[i]; dpp.py:1172-1174 then average that scalar over mask[i]: the scalar itself if sample i has a static element in
+ * both cropped planes, NaN otherwise.  Supported layout: all B elements lie in sample 0; otherwise the term is written as NaN
+ * (the reference raises IndexError or reads into sample 1 there -- the one divergence).
+ * None of these synchronises; no floating-point atomics; counts are unsigned integers converted once.                          */
+/* Replaces dpp.py:1038-1069: clslam_photo_automask_pyramid[_rng] with mask0 (B,H,W) = ('mask',0,0).  noise (4,B,2,H,W), or NULL
+ * with seed != 0 for the in-kernel draw.  partial (4,B,nblk): tile sums over the static pixels; cnt_partial (B,nblk): static
+ * pixels per tile (the same for every scale).  sel / coef_sel as without the mask, for every pixel.                            */
+int clslam_photo_automask_pyramid_masked(const float* warped, const float* target, const float* idmap, const float* noise,
+                                         unsigned long long seed, unsigned long long offset, const float* mask0,
+                                         unsigned char* sel, float* coef_sel, float* partial, unsigned* cnt_partial, int batch,
+                                         int H, int W, void* stream);
+/* The two masked_select calls of dpp.py:1166-1167 as positions: loc [4][2][2 * batch] int per (scale, direction x / y):
+ * [i < batch] = pixel index y * w_s + x of the i-th static element of sample 0's cropped plane, -1 if it has fewer;
+ * [batch + b] = 1 if sample b has a static element in that cropped plane, else 0 (dpp.py:1172-1173).                          */
+int clslam_smooth_locate(const float* const* mask, int* loc, int batch, int H, int W, void* stream);
+/* Replaces dpp.py:1071-1113 under mask_dynamic: clslam_loss_finalize on the masked sums.  Same 18 losses, same smooth_aux; the
+ * smoothness terms sit at loc's positions (n_smooth == batch, or 0 with loc NULL when the per-sample smoothness follows).
+ * mstat [2] = (1 / N_static, N_static) stays on the device for clslam_loss_bwd2_pyramid_masked.                                */
+int clslam_loss_finalize_masked(const clslam_loss_desc* desc, const unsigned* cnt_partial, const int* loc, float* mstat,
+                                void* stream);
+/* Autograd of dpp.py:1068 + 1075: clslam_loss_bwd2_pyramid where a static pixel's term carries inv_n[0] / 4 = 1 / (4 N_static)
+ * in place of sample_w[b] / (H W) / 4 and a dynamic pixel's term carries 0 -- in ddisp_up and in dp_partial alike.             */
+int clslam_loss_bwd2_pyramid_masked(const float* const* disp, const unsigned char* sel, const float* coef_sel, const float* warped,
+                                    const float* target, const float* src_m1, const float* src_p1, const float* inv_k,
+                                    const float* proj, const float* mask0, const float* inv_n, float* ddisp_up, double* dp_partial,
+                                    int batch, int H, int W, float min_depth, float max_depth, void* stream);
+/* Autograd of the positioned terms of dpp.py:1166-1174: ADDS their gradient (and the mean-normalisation feedback) to dz[s] of
+ * sample 0, after clslam_disp_grad_pyramid run with n_smooth = 0.                                                             */
+int clslam_smooth_pos_bwd(const float* const* disp, const float* smooth_aux, const int* loc, int n_smooth, float* const* dz,
+                          int batch, int H, int W, void* stream);
+/* reference_quirks = False under mask_dynamic (the per-sample term dpp.py:1148-1176 evidently meant, on its masks): per sample the
+ * mean of the x terms over the static elements of mask[b,:,:,:-1] plus the mean of the y terms over those of mask[b,:,:-1,:].
+ * partial / cnt [4][B][clslam_smooth_intended_chunks()][2] (x, y); aux [4][B][4] = (inv, T, 1 / n_x, 1 / n_y).  A sample without
+ * a static element in a cropped plane gives NaN.  Otherwise as clslam_smooth_intended_*.                                      */
+int clslam_smooth_intended_masked_fwd(const float* const* disp, const float* const* rgb0, const float* const* mask, float* partial,
+                                      unsigned* cnt, int batch, int H, int W, void* stream);
+int clslam_smooth_intended_masked_finalize(const float* partial, const unsigned* cnt, const float* means, const float* sample_w,
+                                           float* losses, float* aux, int batch, int H, int W, float smooth_scale, void* stream);
+int clslam_smooth_intended_masked_bwd(const float* const* disp, const float* const* rgb0, const float* const* mask,
+                                      const float* aux, const float* sample_w, float* const* dz, int batch, int H, int W,
+                                      float smooth_scale, void* stream);
 /* Pair loss: the photometric loss of ONE source frame at scale 0, forward only.  Replaces dpp.py:602-620
  * (predict_from_images with return_loss: _reconstruct_images of frame -1, i.e. dpp.py:986-1017 with networks/layers.py:51-104
  * and utils.py:120-142, and _compute_loss(scales=(0,)), dpp.py:1038-1113 with networks/layers.py:107-137).
